@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark (BASELINE.json metric): image-text pairs/sec + selective_scan HBM GB/s.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 Workload (value): C2 = ViT-B/16 image tower + Mamba-130M text tower, 224x224
 synthetic images + 77-token synthetic text, batch 256 per GPU, bf16 autocast,
@@ -10,10 +10,20 @@ all-gather for N > 1) + backward (DDP RCCL all-reduce) + fused AdamW +
 logit_scale clamp.  Random-init weights, synthetic data resident in HBM.
 value = N * batch * K / max-over-ranks(time of K steps).
 
+A plain run sets up, warms up, times the K steps and prints the result line.
+--dump-outputs DIR also writes what the last timed step computed (the loss
+dict train_step returns, and a fixed seeded sample of the gradients and the
+updated parameters it leaves behind) as DIR/<name>.npy in float32; weights and
+inputs are seeded, so the same arguments give the same inputs in every run.
+
+--full adds the legs below to the result line (each takes runs of its own).
+
 roofline: the selective-scan forward at C4 (B=64, D=3072, L=4096, N=16, bf16,
 z-gated, softplus) -- the kernel BASELINE.json's HBM target
 names -- timed with HIP events on the stream it is launched on;
 achieved = 6.4594 GB algorithmic bytes per call / average call time.
+
+similarity_fp8: the config-5 fp8 similarity matmul (N = 8192, E = 512).
 
 cpu_baseline: the fp32 CPU restatement (oracle/cpu_model.py) of the same
 C2 training step on a bounded sample (batch 8), rank 0 at N = 1 only.
@@ -64,13 +74,20 @@ def parse():
     ap.add_argument("--input", choices=["resident", "host"], default="resident",
                     help="resident: one synthetic batch in HBM (the `value` definition); host: ISIC-shaped raw "
                          "uint8 crops streamed from pinned host memory each step (data.HostToDeviceLoader)")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the C4 scan roofline, the C5 fp8 similarity and the CPU baselines")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline and similarity legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-batch", type=int, default=8)
     ap.add_argument("--cpu-steps", type=int, default=5)
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="0 = every CPU this process may run on (see _cpu_threads)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def _free_port():
@@ -291,6 +308,36 @@ def cpu_baseline_scan(args):
                       f"bf16 I/O, algorithmic bytes as the roofline ({secs:.1f} s)"}
 
 
+DUMP_SAMPLE = 4096   # elements kept per parameter tensor (some 2 x 7 MB over the C2 model's tensors)
+
+
+def dump_outputs(out_dir, losses, model):
+    """What the last timed step computed, as <out_dir>/<name>.npy in float32: every entry of the loss
+    dict train_step returned, and the gradients and updated parameters it left on the model.  The
+    towers hold ~0.2 G parameters, so of each tensor above DUMP_SAMPLE elements a fixed sample is
+    kept (positions drawn once per tensor from a generator seeded with the tensor's index; the same
+    positions in every run and every build), concatenated in named_parameters() order."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in losses.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), v.detach().float().cpu().numpy().reshape(-1))
+    params, grads = [], []
+    for i, (_, p) in enumerate(model.named_parameters()):
+        flat = p.detach().reshape(-1)
+        grad = None if p.grad is None else p.grad.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(i)
+            idx = torch.randint(flat.numel(), (DUMP_SAMPLE,), generator=g).to(flat.device)
+            flat = flat[idx]
+            grad = None if grad is None else grad[idx]
+        params.append(flat.float().cpu())
+        if grad is not None:
+            grads.append(grad.float().cpu())
+    np.save(os.path.join(out_dir, "params_sample.npy"), torch.cat(params).numpy())
+    np.save(os.path.join(out_dir, "grads_sample.npy"), torch.cat(grads).numpy())
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -412,13 +459,14 @@ def main():
     }
     if args.input == "host":
         feed.close()                              # joins the loader's host thread
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, losses, inner)
     del images, texts, targets, optimizer
     torch.cuda.empty_cache()
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         result["roofline"] = scan_roofline(args.scan_iters)
-    if rank == 0 and not args.no_roofline:
         result["similarity_fp8"] = similarity_c5()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args, args.model)
         result["cpu_baseline_scan"] = cpu_baseline_scan(args)
     if world > 1:

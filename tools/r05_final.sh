@@ -9,10 +9,10 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout
 tail -2 $out/pytest_gpu.log
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1 || { echo "smoke failed"; tail -20 $out/smoke.log; exit 2; }
 tail -1 $out/smoke.log
-timeout -k 10 600 python -u bench.py > $out/bench.json 2> $out/bench.err || { echo "bench failed"; tail -20 $out/bench.err; exit 3; }
+timeout -k 10 600 python -u bench.py --full > $out/bench.json 2> $out/bench.err || { echo "bench failed"; tail -20 $out/bench.err; exit 3; }
 cut -c1-300 $out/bench.json
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $out/prof -o bench --output-format csv \
-  -- python -u bench.py --steps 10 --warmup 3 > $out/prof_bench.json 2> $out/prof.log || { echo "rocprof failed"; tail -20 $out/prof.log; exit 4; }
+  -- python -u bench.py --full --steps 10 --warmup 3 > $out/prof_bench.json 2> $out/prof.log || { echo "rocprof failed"; tail -20 $out/prof.log; exit 4; }
 tr=$(find $out/prof -name "*kernel_trace.csv" | head -1)
 python tools/step_breakdown.py "$tr" 60 > $out/c2_step_breakdown.txt || true
 find $out/prof -name "*kernel_stats.csv" -exec cp {} $out/rocprof_bench_kernel_stats.csv \;
