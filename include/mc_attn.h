@@ -63,6 +63,49 @@ typedef struct {
 /* dq, dk, dv of the above given dout (recomputes the probabilities from q, k and lse). */
 int mc_attn_bwd(const mc_attn_bwd_params* p, void* stream);
 
+/*
+ * Key-padding-masked variant (the BERT text tower: captions padded to the context length):
+ *   o = softmax(scale * q k^T + (key_mask ? 0 : -inf)) v
+ * key_mask is (batch, MC_ATTN_MASK_WORDS) 32-bit words, 4-B aligned: bit j of word t of batch b
+ * set = key 32 t + j may be attended to (HF's attention_mask[:, None, None, :]: one mask per batch
+ * row, shared by its heads and queries, holes allowed).  Bits of keys >= seqlen are ignored.
+ * Every query row is computed, padded ones too (they are rows of the hidden state); lse is over
+ * the valid keys; dk / dv of masked keys are stored as exact zeros.  A 32-key tile whose word is
+ * zero is skipped.  A batch row with no valid key is not a supported input (o, dq, dk, dv come
+ * out zero, lse 0: finite, not HF's uniform average).  Other fields, requirements and return
+ * codes as the unmasked entry points; results are bitwise reproducible (no atomics), and with
+ * every bit set bitwise equal to the unmasked entry points'.
+ */
+#define MC_ATTN_MASK_WORDS (MC_ATTN_MAX_SEQ / 32)
+
+typedef struct {
+  int32_t batch, heads, seqlen, head_dim, dtype;
+  float scale;
+  const void* q; const void* k; const void* v;
+  int64_t q_bs, q_ns, q_hs;
+  void* o; int64_t o_bs, o_ns, o_hs;
+  float* lse;
+  const uint32_t* key_mask;           /* (batch, MC_ATTN_MASK_WORDS) */
+} mc_attn_masked_fwd_params;
+
+int mc_attn_masked_fwd(const mc_attn_masked_fwd_params* p, void* stream);
+
+typedef struct {
+  int32_t batch, heads, seqlen, head_dim, dtype;
+  float scale;
+  const void* q; const void* k; const void* v;
+  int64_t q_bs, q_ns, q_hs;
+  const void* o; const void* dout;
+  int64_t o_bs, o_ns, o_hs;
+  const float* lse;                   /* from mc_attn_masked_fwd with the same key_mask */
+  void* dq; void* dk; void* dv;
+  int64_t dq_bs, dq_ns, dq_hs;
+  float* dsum;
+  const uint32_t* key_mask;           /* (batch, MC_ATTN_MASK_WORDS) */
+} mc_attn_masked_bwd_params;
+
+int mc_attn_masked_bwd(const mc_attn_masked_bwd_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,16 @@
 // g(m) = m ^ ((m & 1) << 2): the row reads of the 32x32x16 operands (ds_read_b128, 16 rows of
 // one chunk per lane group) and the transposed reads (rows r..r+3 x 4 chunks per half-wave) are
 // both conflict-free (64 banks x 4 B).
+//
+// Key-masked variant (mc_attn_masked_fwd / _bwd, the padded captions of the BERT text tower): the
+// same two kernels instantiated with kMask = true; every added instruction sits under
+// `if constexpr (kMask)` and the arguments gain the mask pointer in a derived struct, so the
+// unmasked instantiations compile to what they were.  The words of a batch row (ANDed with the
+// keys < N) live in one VGPR, word t on lane t, and come out wave-uniform through v_readlane: a
+// tile whose word is 0 is skipped by a scalar branch, a tile whose word is all ones takes the
+// unmasked instructions, only a mixed tile pays the per-key selects.
 #include <algorithm>
+#include <type_traits>
 
 #include "mc_common.h"
 #include "../../include/mc_attn.h"
@@ -171,9 +180,30 @@ struct FwdArgs {
   void* o; int64_t o_bs, o_ns, o_hs;
   float* lse;
 };
+struct FwdArgsM : FwdArgs { const uint32_t* mask; };   // (B, kMaskWords) key bits, kMask kernels only
+constexpr int kMaskWords = MC_ATTN_MASK_WORDS;
+template <bool kMask, typename A, typename AM> struct ArgsOf { typedef A type; };
+template <typename A, typename AM> struct ArgsOf<true, A, AM> { typedef AM type; };
 
-template <typename TI, int NT>
-__global__ __launch_bounds__(64 * kFwdWaves, 2) void attn_fwd_kernel(const FwdArgs a) {
+// Mask words of batch row b: lane t < NT holds word t with the bits of keys >= N cleared, every
+// other lane 0.  word_of(wv, t), t wave-uniform, is then a scalar.
+template <int NT>
+__device__ __forceinline__ uint32_t load_mask_words(const uint32_t* mask, int b, int N, int lane) {
+  uint32_t w = 0;
+  if (lane < NT) {
+    const int nb = N - 32 * lane;   // >= 1: NT = ceil(N / 32)
+    w = mask[(int64_t)b * kMaskWords + lane] & (nb >= 32 ? 0xFFFFFFFFu : (1u << nb) - 1u);
+  }
+  return w;
+}
+__device__ __forceinline__ uint32_t word_of(uint32_t wv, int t) {
+  return (uint32_t)__builtin_amdgcn_readlane((int)wv, t);
+}
+// accumulator register r holds row (r & 3) + 8 (r >> 2) + 4 hh of its tile: bit of that row in wl = w >> 4 hh
+__device__ __forceinline__ bool row_bit(uint32_t wl, int r) { return (wl >> ((r & 3) + 8 * (r >> 2))) & 1u; }
+
+template <typename TI, int NT, bool kMask = false>
+__global__ __launch_bounds__(64 * kFwdWaves, 2) void attn_fwd_kernel(const typename ArgsOf<kMask, FwdArgs, FwdArgsM>::type a) {
   using M = M32<TI>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int Np = NT * 32;
@@ -217,16 +247,27 @@ __global__ __launch_bounds__(64 * kFwdWaves, 2) void attn_fwd_kernel(const FwdAr
       *reinterpret_cast<uint4*>(vimg + img_off(r, c)) = vr[j];
     }
   }
+  uint32_t wv = 0;   // kMask: this batch row's mask words (lane t = word t)
+  if constexpr (kMask) wv = load_mask_words<NT>(a.mask, b, N, lane);
   __syncthreads();
   if (qt < NT) {
     // S^T tiles: rows = keys t*32 + (r & 3) + 8 (r >> 2) + 4 hh, column = this lane's query.
     // Two passes over the key tiles (the row max, then the probabilities and P V): recomputing
     // S costs 4 MFMAs per tile and keeps one tile of scores live instead of all NT (no spills).
-    auto s_tile = [&](int t) __attribute__((always_inline)) {
+    // kMask: w = the tile's mask word (keys >= N already cleared); masked keys score -1e30 like
+    // the keys past N, so their probabilities are exactly 0.
+    auto s_tile = [&](int t, uint32_t w) __attribute__((always_inline)) {
       f32x16 acc = {};
 #pragma unroll
       for (int s = 0; s < 4; ++s) acc = M::mma(row_chunk(kimg, t * 32 + l32, 2 * s + hh), qf[s], acc);
-      if (t == NT - 1 && Np > N) {   // keys past N (last tile only)
+      if constexpr (kMask) {
+        if (w != 0xFFFFFFFFu) {   // wave-uniform
+          const uint32_t wl = w >> (4 * hh);
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if (!row_bit(wl, r)) acc[r] = -1e30f;
+        }
+      } else if (t == NT - 1 && Np > N) {   // keys past N (last tile only)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
           if (t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh >= N) acc[r] = -1e30f;
@@ -236,7 +277,12 @@ __global__ __launch_bounds__(64 * kFwdWaves, 2) void attn_fwd_kernel(const FwdAr
     float m = -1e30f;
 #pragma unroll 1
     for (int t = 0; t < NT; ++t) {
-      const f32x16 st = s_tile(t);
+      uint32_t w = 0;
+      if constexpr (kMask) {
+        w = word_of(wv, t);
+        if (w == 0) continue;   // no valid key in the tile
+      }
+      const f32x16 st = s_tile(t, w);
 #pragma unroll
       for (int r = 0; r < 16; ++r) m = fmaxf(m, st[r]);
     }
@@ -247,7 +293,12 @@ __global__ __launch_bounds__(64 * kFwdWaves, 2) void attn_fwd_kernel(const FwdAr
     f32x16 o0 = {}, o1 = {};
 #pragma unroll 1
     for (int t = 0; t < NT; ++t) {
-      f32x16 st = s_tile(t);
+      uint32_t w = 0;
+      if constexpr (kMask) {
+        w = word_of(wv, t);
+        if (w == 0) continue;
+      }
+      f32x16 st = s_tile(t, w);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float p = fast_exp2(st[r] * a.c2 - mc);
@@ -263,9 +314,16 @@ __global__ __launch_bounds__(64 * kFwdWaves, 2) void attn_fwd_kernel(const FwdAr
       }
     }
     l = swap_sum(l);
+    if constexpr (kMask) {   // no valid key at all (unsupported input): o = 0, lse = 0, not NaN / -inf
+      const bool none = l == 0.f;
+      store_rows<TI>(reinterpret_cast<TI*>(a.o) + (int64_t)b * a.o_bs + (int64_t)h * a.o_hs, a.o_ns, q, N, lane, o0, o1,
+                     none ? 0.f : 1.f / l);
+      if (hh == 0 && q < N) a.lse[(int64_t)bh * N + q] = none ? 0.f : m * a.scale + fast_log2(l) * kLn2;
+    } else {
     store_rows<TI>(reinterpret_cast<TI*>(a.o) + (int64_t)b * a.o_bs + (int64_t)h * a.o_hs, a.o_ns, q, N, lane, o0, o1,
                    1.f / l);
     if (hh == 0 && q < N) a.lse[(int64_t)bh * N + q] = m * a.scale + fast_log2(l) * kLn2;
+    }
   }
 }
 
@@ -281,9 +339,10 @@ struct BwdArgs {
   int64_t d_bs, d_ns, d_hs;
   float* dsum;   // (B, 3, H, 64) or null
 };
+struct BwdArgsM : BwdArgs { const uint32_t* mask; };
 
-template <typename TI, int NT>
-__global__ __launch_bounds__(64 * kBwdWaves, 1) void attn_bwd_kernel(const BwdArgs a) {
+template <typename TI, int NT, bool kMask = false>
+__global__ __launch_bounds__(64 * kBwdWaves, 1) void attn_bwd_kernel(const typename ArgsOf<kMask, BwdArgs, BwdArgsM>::type a) {
   using M = M32<TI>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int Np = NT * 32;
@@ -341,6 +400,8 @@ __global__ __launch_bounds__(64 * kBwdWaves, 1) void attn_bwd_kernel(const BwdAr
   const TI* vg = reinterpret_cast<const TI*>(a.v) + off;
   const TI* og = reinterpret_cast<const TI*>(a.o) + offo;
   const TI* gg = reinterpret_cast<const TI*>(a.g) + offo;
+  uint32_t wv = 0;   // kMask: the mask words of this head's batch row (re-read per head: b changes)
+  if constexpr (kMask) wv = load_mask_words<NT>(a.mask, b, N, lane);
 
   if constexpr (kPersist) {
     // ---- K / V of this head (registers -> images), delta from the streamed dO / O images, lse2
@@ -431,8 +492,13 @@ __global__ __launch_bounds__(64 * kBwdWaves, 1) void attn_bwd_kernel(const BwdAr
       vf[s] = row_chunk(vimg, kt * 32 + l32, 2 * s + hh);
     }
     f32x16 dk0 = {}, dk1 = {}, dv0 = {}, dv1 = {};
+    // kMask: the key is this lane's column of all four accumulators and of P / dS, so a masked key
+    // touches nothing but its own dK / dV rows: they are cleared after the sweep (a select, so an
+    // overflowed P of a masked key cannot leave a NaN), and a tile without a valid key skips the sweep.
+    uint32_t kw = 0xFFFFFFFFu;
+    if constexpr (kMask) kw = word_of(wv, kt);
 #pragma unroll 1
-    for (int qt = 0; qt < NT; ++qt) {
+    for (int qt = 0; qt < (kw != 0 ? NT : 0); ++qt) {
       f32x16 sa = {}, pa = {};
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
@@ -460,6 +526,9 @@ __global__ __launch_bounds__(64 * kBwdWaves, 1) void attn_bwd_kernel(const BwdAr
         dk0 = M::mma(tr_chunk(qimg, r0, g16, lane), df, dk0);
         dk1 = M::mma(tr_chunk(qimg, r0, 32 + g16, lane), df, dk1);
       }
+    }
+    if constexpr (kMask) {
+      if (kw != 0xFFFFFFFFu && !((kw >> l32) & 1u)) dk0 = dk1 = dv0 = dv1 = f32x16{};
     }
     const int64_t doff = (int64_t)b * a.d_bs + (int64_t)h * a.d_hs;
     store_rows<TI>(reinterpret_cast<TI*>(a.dk) + doff, a.d_ns, kt * 32 + l32, N, lane, dk0, dk1, a.scale,
@@ -489,6 +558,11 @@ __global__ __launch_bounds__(64 * kBwdWaves, 1) void attn_bwd_kernel(const BwdAr
     f32x16 dq0 = {}, dq1 = {};
 #pragma unroll 1
     for (int kt = 0; kt < NT; ++kt) {
+      uint32_t w = 0;
+      if constexpr (kMask) {
+        w = word_of(wv, kt);
+        if (w == 0) continue;   // no valid key in the tile: dS = 0
+      }
       f32x16 sa = {}, pa = {};
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
@@ -499,6 +573,14 @@ __global__ __launch_bounds__(64 * kBwdWaves, 1) void attn_bwd_kernel(const BwdAr
       for (int r = 0; r < 16; ++r) {
         const float p = fast_exp2(sa[r] * a.c2 - L);
         pa[r] = p * (pa[r] - Dl);
+      }
+      if constexpr (kMask) {
+        if (w != 0xFFFFFFFFu) {   // keys on the accumulator rows, as in the forward
+          const uint32_t wl = w >> (4 * hh);
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if (!row_bit(wl, r)) pa[r] = 0.f;
+        }
       }
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
@@ -541,18 +623,21 @@ static int num_cus() {
   return n;
 }
 
-template <typename TI, int NT>
-void launch_fwd_nt(const FwdArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL((attn_fwd_kernel<TI, NT>), dim3(a.B * a.H), dim3(64 * kFwdWaves), fwd_lds(NT), s, a);
+// A = FwdArgs / BwdArgs: the unmasked kernels; A = FwdArgsM / BwdArgsM: the kMask instantiations
+template <typename TI, int NT, typename A>
+void launch_fwd_nt(const A& a, hipStream_t s) {
+  constexpr bool kMask = std::is_same<A, FwdArgsM>::value;
+  hipLaunchKernelGGL((attn_fwd_kernel<TI, NT, kMask>), dim3(a.B * a.H), dim3(64 * kFwdWaves), fwd_lds(NT), s, a);
 }
-template <typename TI, int NT>
-void launch_bwd_nt(const BwdArgs& a, hipStream_t s) {
+template <typename TI, int NT, typename A>
+void launch_bwd_nt(const A& a, hipStream_t s) {
+  constexpr bool kMask = std::is_same<A, BwdArgsM>::value;
   // NT <= 7: persistent, one workgroup per CU walks the heads (the LDS of one head fills the CU)
   const int grid = NT <= 7 ? std::min(a.B * a.H, num_cus()) : a.B * a.H;
-  hipLaunchKernelGGL((attn_bwd_kernel<TI, NT>), dim3(grid), dim3(64 * kBwdWaves), bwd_lds(NT), s, a);
+  hipLaunchKernelGGL((attn_bwd_kernel<TI, NT, kMask>), dim3(grid), dim3(64 * kBwdWaves), bwd_lds(NT), s, a);
 }
-template <typename TI>
-void launch_fwd(const FwdArgs& a, hipStream_t s) {
+template <typename TI, typename A>
+void launch_fwd(const A& a, hipStream_t s) {
   switch ((a.N + 31) / 32) {
     case 1: launch_fwd_nt<TI, 1>(a, s); break;
     case 2: launch_fwd_nt<TI, 2>(a, s); break;
@@ -564,8 +649,8 @@ void launch_fwd(const FwdArgs& a, hipStream_t s) {
     default: launch_fwd_nt<TI, 8>(a, s); break;
   }
 }
-template <typename TI>
-void launch_bwd(const BwdArgs& a, hipStream_t s) {
+template <typename TI, typename A>
+void launch_bwd(const A& a, hipStream_t s) {
   switch ((a.N + 31) / 32) {
     case 1: launch_bwd_nt<TI, 1>(a, s); break;
     case 2: launch_bwd_nt<TI, 2>(a, s); break;
@@ -594,15 +679,20 @@ static int check_common(int B, int H, int N, int D, int dtype, const char* who) 
 
 using namespace mc;
 
-extern "C" int mc_attn_fwd(const mc_attn_fwd_params* p, void* stream) {
-  MC_CHECK(p, MC_ERR_INVALID, "mc_attn_fwd: null params");
-  const int rc = attn::check_common(p->batch, p->heads, p->seqlen, p->head_dim, p->dtype, "mc_attn_fwd");
+// Shared by the unmasked and the masked entry points (P: the parameter struct, A: FwdArgs[M] / BwdArgs[M])
+template <typename P, typename A>
+static int run_fwd(const P* p, A& a, void* stream, const char* who) {
+  MC_CHECK(p, MC_ERR_INVALID, "%s: null params", who);
+  const int rc = attn::check_common(p->batch, p->heads, p->seqlen, p->head_dim, p->dtype, who);
   if (rc != MC_OK) return rc;
   MC_CHECK(attn::rows_ok(p->q, p->q_bs, p->q_ns, p->q_hs) && attn::rows_ok(p->k, p->q_bs, p->q_ns, p->q_hs) &&
                attn::rows_ok(p->v, p->q_bs, p->q_ns, p->q_hs) && attn::rows_ok(p->o, p->o_bs, p->o_ns, p->o_hs) && p->lse,
-           MC_ERR_INVALID, "mc_attn_fwd: q / k / v / o need 16-B aligned rows (strides %% 8 elements), lse non-null");
+           MC_ERR_INVALID, "%s: q / k / v / o need 16-B aligned rows (strides %% 8 elements), lse non-null", who);
+  if constexpr (std::is_same<A, attn::FwdArgsM>::value) {
+    MC_CHECK(p->key_mask && ((uintptr_t)p->key_mask & 3) == 0, MC_ERR_INVALID, "%s: key_mask null or not 4-B aligned", who);
+    a.mask = p->key_mask;
+  }
   if (p->batch == 0) return MC_OK;
-  attn::FwdArgs a;
   a.B = p->batch; a.H = p->heads; a.N = p->seqlen;
   a.scale = p->scale; a.c2 = p->scale * kLog2e;
   a.q = p->q; a.k = p->k; a.v = p->v;
@@ -612,22 +702,26 @@ extern "C" int mc_attn_fwd(const mc_attn_fwd_params* p, void* stream) {
   if (p->dtype == MC_DTYPE_BF16) attn::launch_fwd<bf16_t>(a, (hipStream_t)stream);
   else attn::launch_fwd<f16_t>(a, (hipStream_t)stream);
   const hipError_t e = hipGetLastError();
-  MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "mc_attn_fwd: launch failed: %s", hipGetErrorString(e));
+  MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e));
   return MC_OK;
 }
 
-extern "C" int mc_attn_bwd(const mc_attn_bwd_params* p, void* stream) {
-  MC_CHECK(p, MC_ERR_INVALID, "mc_attn_bwd: null params");
-  const int rc = attn::check_common(p->batch, p->heads, p->seqlen, p->head_dim, p->dtype, "mc_attn_bwd");
+template <typename P, typename A>
+static int run_bwd(const P* p, A& a, void* stream, const char* who) {
+  MC_CHECK(p, MC_ERR_INVALID, "%s: null params", who);
+  const int rc = attn::check_common(p->batch, p->heads, p->seqlen, p->head_dim, p->dtype, who);
   if (rc != MC_OK) return rc;
   MC_CHECK(attn::rows_ok(p->q, p->q_bs, p->q_ns, p->q_hs) && attn::rows_ok(p->k, p->q_bs, p->q_ns, p->q_hs) &&
                attn::rows_ok(p->v, p->q_bs, p->q_ns, p->q_hs) && attn::rows_ok(p->o, p->o_bs, p->o_ns, p->o_hs) &&
                attn::rows_ok(p->dout, p->o_bs, p->o_ns, p->o_hs) && attn::rows_ok(p->dq, p->dq_bs, p->dq_ns, p->dq_hs) &&
                attn::rows_ok(p->dk, p->dq_bs, p->dq_ns, p->dq_hs) && attn::rows_ok(p->dv, p->dq_bs, p->dq_ns, p->dq_hs) &&
                p->lse,
-           MC_ERR_INVALID, "mc_attn_bwd: every tensor needs 16-B aligned rows (strides %% 8 elements), lse non-null");
+           MC_ERR_INVALID, "%s: every tensor needs 16-B aligned rows (strides %% 8 elements), lse non-null", who);
+  if constexpr (std::is_same<A, attn::BwdArgsM>::value) {
+    MC_CHECK(p->key_mask && ((uintptr_t)p->key_mask & 3) == 0, MC_ERR_INVALID, "%s: key_mask null or not 4-B aligned", who);
+    a.mask = p->key_mask;
+  }
   if (p->batch == 0) return MC_OK;
-  attn::BwdArgs a;
   a.B = p->batch; a.H = p->heads; a.N = p->seqlen;
   a.scale = p->scale; a.c2 = p->scale * kLog2e;
   a.q = p->q; a.k = p->k; a.v = p->v;
@@ -640,6 +734,23 @@ extern "C" int mc_attn_bwd(const mc_attn_bwd_params* p, void* stream) {
   if (p->dtype == MC_DTYPE_BF16) attn::launch_bwd<bf16_t>(a, (hipStream_t)stream);
   else attn::launch_bwd<f16_t>(a, (hipStream_t)stream);
   const hipError_t e = hipGetLastError();
-  MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "mc_attn_bwd: launch failed: %s", hipGetErrorString(e));
+  MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e));
   return MC_OK;
+}
+
+extern "C" int mc_attn_fwd(const mc_attn_fwd_params* p, void* stream) {
+  attn::FwdArgs a;
+  return run_fwd(p, a, stream, "mc_attn_fwd");
+}
+extern "C" int mc_attn_bwd(const mc_attn_bwd_params* p, void* stream) {
+  attn::BwdArgs a;
+  return run_bwd(p, a, stream, "mc_attn_bwd");
+}
+extern "C" int mc_attn_masked_fwd(const mc_attn_masked_fwd_params* p, void* stream) {
+  attn::FwdArgsM a;
+  return run_fwd(p, a, stream, "mc_attn_masked_fwd");
+}
+extern "C" int mc_attn_masked_bwd(const mc_attn_masked_bwd_params* p, void* stream) {
+  attn::BwdArgsM a;
+  return run_bwd(p, a, stream, "mc_attn_masked_bwd");
 }

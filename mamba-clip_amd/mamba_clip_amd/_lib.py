@@ -165,6 +165,19 @@ class AttnBwdParams(ctypes.Structure):
     ]
 
 
+class AttnMaskedFwdParams(ctypes.Structure):
+    """Mirror of ``mc_attn_masked_fwd_params`` (include/mc_attn.h)."""
+    _fields_ = AttnFwdParams._fields_ + [("key_mask", c_vp)]
+
+
+class AttnMaskedBwdParams(ctypes.Structure):
+    """Mirror of ``mc_attn_masked_bwd_params`` (include/mc_attn.h)."""
+    _fields_ = AttnBwdParams._fields_ + [("key_mask", c_vp)]
+
+
+MC_ATTN_MASK_WORDS = 8   # 32-bit key-mask words per batch row (MC_ATTN_MAX_SEQ / 32)
+
+
 class SS2DConvParams(ctypes.Structure):
     """Mirror of ``mc_ss2d_conv_params`` (include/mc_ss2d.h)."""
     _fields_ = [
@@ -315,6 +328,8 @@ SYMBOLS = {
                                      c_i64, c_vp]),
     "mc_attn_fwd": (ctypes.c_int, [ctypes.POINTER(AttnFwdParams), c_vp]),
     "mc_attn_bwd": (ctypes.c_int, [ctypes.POINTER(AttnBwdParams), c_vp]),
+    "mc_attn_masked_fwd": (ctypes.c_int, [ctypes.POINTER(AttnMaskedFwdParams), c_vp]),
+    "mc_attn_masked_bwd": (ctypes.c_int, [ctypes.POINTER(AttnMaskedBwdParams), c_vp]),
     "mc_mixer_proj_fwd": (ctypes.c_int, [ctypes.POINTER(MixerProjParams), c_vp]),
     "mc_mixer_proj_bwd": (ctypes.c_int, [ctypes.POINTER(MixerProjBwdParams), c_vp]),
     "mc_patch_embed_input": (ctypes.c_int, [ctypes.POINTER(PatchInputParams), c_vp]),

@@ -46,7 +46,8 @@ def build_parser():
     p.add_argument("--stage", type=int, default=1, choices=[1, 2])
     p.add_argument("--model", type=str, default="vit_b16-mamba130m",
                    help="stage-1 model config (offline: vit_b16-mamba130m, tiny-mamba-clip, mamba790m-text, "
-                        "biomedclip-vit_b16-pubmedbert256)")
+                        "biomedclip-vit_b16-pubmedbert256, biomedclip-vit_b16-pubmedbert256-hf: the text "
+                        "tower that computes HF BertModel)")
     p.add_argument("--model-stage-1", type=str, default=None, help="alias of --model for stage 2")
     p.add_argument("--model-stage-2", type=str, default="ClipClassifier")
     p.add_argument("--use-inner-prod", action="store_true")

@@ -16,6 +16,7 @@ SURVEY.md 8c) are defined here and random-initialised:
   MambaTextEncoder   Mamba LM text tower (Mamba-130M: 24 x d_model 768,
                      d_inner 1536, d_state 16, RMSNorm, fp32 residual stream)
   BertTextEncoder    PubMedBERT-base shape (12 x 768, ctx 256) for BiomedCLIP
+  HFBertTextEncoder  the same tower computing transformers.BertModel (post-LN, token types, padding mask)
 Hot ops run on the HIP library: selective scan, causal conv1d, fused
 add+RMSNorm / add+LayerNorm, patch im2col, short-sequence attention
 (attention.hip), contrastive loss; dense projections are plain library GEMMs
@@ -34,7 +35,7 @@ import torch.utils.checkpoint
 from . import GEMM_GRIDS_DATA_PARALLEL
 from .ops import (GradHandoff, GradSlab, _compute_dtype, add_layernorm, add_pos, add_rmsnorm, attn_supported,
                   causal_conv1d, l2_normalize, linear_sk, mixer_proj, mixer_proj_ok, mlp, neg_exp_many,
-                  packed_attention, patch_im2col, qkv_proj, split_rows, split_rows_n, ss2d_conv_stack,
+                  pack_key_mask, packed_attention, patch_im2col, qkv_proj, split_rows, split_rows_n, ss2d_conv_stack,
                   ss2d_merge_ln_gate, ss2d_proj, ss2d_proj_ok, token_embed, weight_cast_scope, wleft_mm)
 from .selective_scan_interface import (SS2D_REVERSE_GROUPS, SS2D_U_GROUPS, ProjectedScanFn, SelectiveScanFn,
                                        fine_state_scope,
@@ -280,25 +281,37 @@ class Attention(nn.Module):
         self.proj = nn.Linear(dim, dim)
         self.fused_attention = True   # mc_attn_fwd/bwd where supported (bf16/f16, head_dim 64, N <= 256)
 
-    def forward(self, x):
+    last_path = None   # "fused" / "sdpa": what the latest forward ran (tests assert the kernel under test)
+
+    def forward(self, x, key_mask=None, valid=None):
+        """valid: (B, N) bool key-padding mask (HF attention_mask[:, None, None, :]), None = attend to
+        every key; key_mask: its pack_key_mask words, packed once per tower forward (packed here if
+        the fused path needs them and only `valid` came)."""
         Bsz, N, C = x.shape
+        if valid is None and key_mask is not None:
+            raise ValueError("Attention: key_mask needs the boolean `valid` it was packed from")
         if self.fused_attention and x.is_cuda and attn_supported(N, C // self.heads, _compute_dtype(x)):
             # packed qkv projection -> fused attention kernel (ops.PackedAttentionFn: the whole
             # sequence of a head in LDS) -> output projection; o is already (B, N, C) and the
             # backward writes dq / dk / dv into the packed projection gradient
+            self.last_path = "fused"
             qkv = linear_sk(x, self.qkv.weight, self.qkv.bias)
-            return linear_sk(packed_attention(qkv, self.heads), self.proj.weight, self.proj.bias)
+            if valid is not None and key_mask is None:
+                key_mask = pack_key_mask(valid)
+            return linear_sk(packed_attention(qkv, self.heads, key_mask), self.proj.weight, self.proj.bias)
+        self.last_path = "sdpa"
         # unbind (not index) the q/k/v slices: its backward stacks the three
         # gradients in one write instead of zero-filling and accumulating a
         # (3, B, H, N, D) buffer three times and copying it contiguous again
         # q, k, v: (B, H, N, D) views of the packed qkv output; the backward packs dq / dk / dv and
         # the qkv bias gradient in one pass (ops.QKVProjFn)
         q, k, v = qkv_proj(x, self.qkv.weight, self.qkv.bias, self.heads)
+        am = valid[:, None, None, :] if valid is not None else None   # True = attend
         if x.is_cuda:
             with _gpu_sdpa_backends():
-                o = F.scaled_dot_product_attention(q, k, v)
+                o = F.scaled_dot_product_attention(q, k, v, attn_mask=am)
         else:
-            o = F.scaled_dot_product_attention(q, k, v)
+            o = F.scaled_dot_product_attention(q, k, v, attn_mask=am)
         return linear_sk(o.transpose(1, 2).reshape(Bsz, N, C), self.proj.weight, self.proj.bias)
 
 
@@ -398,6 +411,139 @@ class BertTextEncoder(nn.Module):
         return self.proj(m[:, 0] + h[:, 0])
 
 
+# ============================================================================ HF-faithful BERT text tower
+class PostLNBlock(nn.Module):
+    """One transformers.BertLayer: post-LN, h1 = LN(x + attn(x, mask)); h2 = LN(h1 + fc2(gelu(fc1(h1))))
+    with eps 1e-12 and the exact (erf) GELU of hidden_act="gelu".  Each residual add is the fused
+    add + LayerNorm (mc_add_layernorm) whose normalised output is the next input."""
+
+    def __init__(self, dim, heads, mlp_dim, eps=1e-12):
+        super().__init__()
+        self.attn = Attention(dim, heads)
+        self.norm1 = nn.LayerNorm(dim, eps=eps)
+        self.fc1 = nn.Linear(dim, mlp_dim)
+        self.fc2 = nn.Linear(mlp_dim, dim)
+        self.norm2 = nn.LayerNorm(dim, eps=eps)
+
+    def forward(self, x, key_mask=None, valid=None):
+        # the hidden state comes first: add_layernorm works in its first operand's dtype, so under
+        # autocast the LayerNorm outputs stay fp32 as they do in HF (the projections cast their input)
+        h1 = add_layernorm(x, self.attn(x, key_mask, valid), self.norm1.weight, self.norm1.bias, self.norm1.eps)[0]
+        m = mlp(h1, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias)
+        return add_layernorm(h1, m, self.norm2.weight, self.norm2.bias, self.norm2.eps)[0]
+
+
+class HFBertTextEncoder(nn.Module):
+    """transformers.BertModel (add_pooling_layer=False) as BiomedCLIP's text tower: word + position +
+    token-type-0 embeddings -> LayerNorm (eps 1e-12) -> post-LN layers that attend only to
+    tokens != pad_token_id -> the CLS row of the last hidden state -> the bias-free Linear-GELU-Linear
+    projection of BertTextEncoder.  load_hf_bert_state_dict fills it from an HF-named state dict;
+    tests/golden/bert_hf_tiny.safetensors pins it to transformers.  Padded query rows are computed (they
+    are rows of last_hidden_state); the fused attention skips key tiles that are all padding."""
+
+    def __init__(self, vocab_size=30522, context_length=256, max_positions=512, type_vocab_size=2, width=768,
+                 layers=12, heads=12, output_dim=512, pad_token_id=0, mlp_dim=None):
+        super().__init__()
+        self.vocab_size, self.context_length, self.output_dim = vocab_size, context_length, output_dim
+        self.pad_token_id = pad_token_id
+        self.tok = nn.Embedding(vocab_size, width)
+        self.pos = nn.Embedding(max_positions, width)
+        self.tok_type = nn.Embedding(type_vocab_size, width)
+        self.ln = nn.LayerNorm(width, eps=1e-12)
+        self.blocks = nn.ModuleList([PostLNBlock(width, heads, mlp_dim or 4 * width) for _ in range(layers)])
+        self.proj = nn.Sequential(nn.Linear(width, (width + output_dim) // 2, bias=False), nn.GELU(),
+                                  nn.Linear((width + output_dim) // 2, output_dim, bias=False))
+        for m in self.modules():   # HF BertPreTrainedModel._init_weights (initializer_range 0.02)
+            if isinstance(m, (nn.Linear, nn.Embedding)):
+                nn.init.normal_(m.weight, std=0.02)
+                if getattr(m, "bias", None) is not None:
+                    nn.init.zeros_(m.bias)
+
+    def lock_units(self):
+        """(embeddings incl. their LayerNorm, [layer, ...], nothing after) for lock_text_tower."""
+        return ([("tok.weight", self.tok.weight), ("pos.weight", self.pos.weight), ("tok_type.weight", self.tok_type.weight),
+                 ("ln.weight", self.ln.weight), ("ln.bias", self.ln.bias)],
+                [list(b.named_parameters(prefix=f"blocks.{i}")) for i, b in enumerate(self.blocks)], [])
+
+    grad_checkpointing = False
+
+    def set_grad_checkpointing(self, enable=True):
+        """Activation checkpointing per encoder layer (HF gradient_checkpointing semantics)."""
+        self.grad_checkpointing = bool(enable)
+
+    def forward_hidden(self, tokens):
+        """last_hidden_state of the HF model, (B, N, width)."""
+        N = tokens.shape[1]
+        if N > self.pos.num_embeddings:
+            raise ValueError(f"{N} tokens, the position table has {self.pos.num_embeddings}")
+        valid = tokens != self.pad_token_id
+        # position rows 0..N-1 plus token-type row 0, one (1, N, width) table added to every caption
+        x = self.ln(add_pos(self.tok(tokens), (self.pos.weight[:N] + self.tok_type.weight[0]).unsqueeze(0)))
+        # the key bits of the fused kernel, packed once for all layers (no sync); fp32 / CPU: SDPA takes `valid`
+        a0 = self.blocks[0].attn
+        fused = a0.fused_attention and x.is_cuda and attn_supported(N, x.shape[-1] // a0.heads, _compute_dtype(x))
+        key_mask = pack_key_mask(valid) if fused else None
+        ckpt = self.grad_checkpointing and torch.is_grad_enabled()
+        for blk in self.blocks:
+            if ckpt:
+                x = torch.utils.checkpoint.checkpoint(blk, x, key_mask, valid, use_reentrant=False)
+            else:
+                x = blk(x, key_mask, valid)
+        return x
+
+    def forward(self, tokens):
+        return self.proj(self.forward_hidden(tokens)[:, 0])
+
+    def load_hf_bert_state_dict(self, sd):
+        return load_hf_bert_state_dict(self, sd)
+
+
+_HF_BERT_IGNORED = ("pooler.", "embeddings.position_ids")
+_HF_BERT_LAYER = {   # HF BertLayer name -> PostLNBlock name (query / key / value go into the packed qkv)
+    "attention.output.dense": "attn.proj", "attention.output.LayerNorm": "norm1",
+    "intermediate.dense": "fc1", "output.dense": "fc2", "output.LayerNorm": "norm2",
+}
+
+
+def load_hf_bert_state_dict(model, sd):
+    """Copy a transformers.BertModel state dict (HF names, with or without a leading "bert.") into an
+    HFBertTextEncoder.  Strict: a missing or an unexpected key raises KeyError; only pooler.* and
+    embeddings.position_ids are ignored (the tower pools the CLS row itself).  The projection after the
+    CLS row is not part of BertModel and keeps its values."""
+    sd = {(k[5:] if k.startswith("bert.") else k): v for k, v in sd.items()}
+    sd = {k: v for k, v in sd.items() if not k.startswith(_HF_BERT_IGNORED)}
+    want = {"embeddings.word_embeddings.weight": model.tok.weight,
+            "embeddings.position_embeddings.weight": model.pos.weight,
+            "embeddings.token_type_embeddings.weight": model.tok_type.weight,
+            "embeddings.LayerNorm.weight": model.ln.weight, "embeddings.LayerNorm.bias": model.ln.bias}
+    packed = {}
+    for i, blk in enumerate(model.blocks):
+        pre = f"encoder.layer.{i}."
+        for hf, ours in _HF_BERT_LAYER.items():
+            mod = blk.get_submodule(ours)
+            want[f"{pre}{hf}.weight"], want[f"{pre}{hf}.bias"] = mod.weight, mod.bias
+        for wb in ("weight", "bias"):
+            names = [f"{pre}attention.self.{n}.{wb}" for n in ("query", "key", "value")]
+            packed[tuple(names)] = getattr(blk.attn.qkv, wb)
+    expected = set(want) | {n for names in packed for n in names}
+    missing, unexpected = sorted(expected - set(sd)), sorted(set(sd) - expected)
+    if missing or unexpected:
+        raise KeyError(f"load_hf_bert_state_dict: missing {missing}, unexpected {unexpected}")
+    with torch.no_grad():
+        for name, param in want.items():
+            if sd[name].shape != param.shape:
+                raise ValueError(f"load_hf_bert_state_dict: {name} is {tuple(sd[name].shape)}, "
+                                 f"the tower has {tuple(param.shape)}")
+            param.copy_(sd[name])
+        for names, param in packed.items():
+            cat = torch.cat([sd[n] for n in names], 0)
+            if cat.shape != param.shape:
+                raise ValueError(f"load_hf_bert_state_dict: {names[0]} (+ key, value) pack to {tuple(cat.shape)}, "
+                                 f"the tower has {tuple(param.shape)}")
+            param.copy_(cat)
+    return model
+
+
 # ============================================================================ CLIP wrapper (model.py:998-1112)
 def _is_norm_param(name):
     """Parameters of the modules the reference's lock_text_tower keeps under `freeze_layer_norm`:
@@ -446,7 +592,7 @@ class ClipModel(nn.Module):
         env = os.environ.get("MAMBA_CLIP_AMD_SIDE_PRIORITY")
         if env is not None:
             return int(env)
-        return -1 if isinstance(self.text, BertTextEncoder) else 0
+        return -1 if isinstance(self.text, (BertTextEncoder, HFBertTextEncoder)) else 0
 
     @property
     def side_tower(self):
@@ -896,13 +1042,19 @@ MODEL_CONFIGS = {
                                                      n_layer=48, output_dim=512)),
     # C3: BiomedCLIP-shaped (ViT-B/16 + PubMedBERT-256), random init (BASELINE configs[2])
     "biomedclip-vit_b16-pubmedbert256": dict(vision=dict(), bert=dict()),
+    # C3 with the text tower that computes transformers.BertModel (post-LN, token types, padding mask):
+    # the one BiomedCLIP's PubMedBERT weights load into (load_hf_bert_state_dict)
+    "biomedclip-vit_b16-pubmedbert256-hf": dict(vision=dict(), hf_bert=dict()),
 }
 
 
 def build_clip(name):
     cfg = MODEL_CONFIGS[name]
     visual = VisionTransformer(**cfg["vision"])
-    text = BertTextEncoder(**cfg["bert"]) if "bert" in cfg else MambaTextEncoder(**cfg["text"])
+    if "hf_bert" in cfg:
+        text = HFBertTextEncoder(**cfg["hf_bert"])
+    else:
+        text = BertTextEncoder(**cfg["bert"]) if "bert" in cfg else MambaTextEncoder(**cfg["text"])
     return ClipModel(visual, text)
 
 

@@ -1600,6 +1600,73 @@ def attn_supported(seqlen, head_dim, dtype):
     return head_dim == 64 and 1 <= seqlen <= 256 and dtype in (torch.bfloat16, torch.float16)
 
 
+def _packed_attn_fwd(ctx, qkv, heads, words):
+    """Forward of PackedAttentionFn (words None: mc_attn_fwd) and PackedMaskedAttentionFn
+    (words (B, 8) int32 key bits: mc_attn_masked_fwd)."""
+    Bsz, N, C3 = qkv.shape
+    C = C3 // 3
+    D = C // heads
+    if not (qkv.is_cuda and attn_supported(N, D, qkv.dtype)):
+        raise RuntimeError(f"packed_attention: unsupported (device {qkv.device}, N {N}, head_dim {D}, "
+                           f"{qkv.dtype}); bf16/f16 on the GPU, head_dim 64, N <= 256")
+    lib = _lib.load()
+    y = _hip_rows(qkv.reshape(Bsz * N, C3), 8, "packed_attention").view(Bsz, N, C3)
+    o = torch.empty(Bsz, N, C, device=qkv.device, dtype=qkv.dtype)
+    lse = torch.empty(Bsz, heads, N, device=qkv.device, dtype=torch.float32)
+    p = _lib.AttnFwdParams() if words is None else _lib.AttnMaskedFwdParams()
+    p.batch, p.heads, p.seqlen, p.head_dim, p.dtype = Bsz, heads, N, D, _lib.dtype_code(qkv.dtype)
+    p.scale = D ** -0.5
+    es = y.element_size()
+    p.q, p.k, p.v = y.data_ptr(), y.data_ptr() + C * es, y.data_ptr() + 2 * C * es
+    p.q_bs, p.q_ns, p.q_hs = y.stride(0), y.stride(1), D
+    p.o, p.o_bs, p.o_ns, p.o_hs = o.data_ptr(), o.stride(0), o.stride(1), D
+    p.lse = lse.data_ptr()
+    if words is None:
+        _lib.check(lib.mc_attn_fwd(p, _lib.stream_handle(qkv.device)), "mc_attn_fwd")
+        ctx.save_for_backward(y, o, lse)
+    else:
+        p.key_mask = words.data_ptr()
+        _lib.check(lib.mc_attn_masked_fwd(p, _lib.stream_handle(qkv.device)), "mc_attn_masked_fwd")
+        ctx.save_for_backward(y, o, lse, words)
+    ctx.heads = heads
+    return o
+
+
+def _packed_attn_bwd(ctx, go):
+    saved = ctx.saved_tensors   # read once (activation checkpointing unpacks on every read)
+    y, o, lse = saved[:3]
+    words = saved[3] if len(saved) > 3 else None
+    Bsz, N, C3 = y.shape
+    C = C3 // 3
+    D = C // ctx.heads
+    lib = _lib.load()
+    g = _hip_rows(go.to(o.dtype).reshape(Bsz * N, C), 8, "packed_attention backward").view(Bsz, N, C)
+    dy = torch.empty_like(y)
+    p = _lib.AttnBwdParams() if words is None else _lib.AttnMaskedBwdParams()
+    p.batch, p.heads, p.seqlen, p.head_dim, p.dtype = Bsz, ctx.heads, N, D, _lib.dtype_code(y.dtype)
+    p.scale = D ** -0.5
+    es = y.element_size()
+    p.q, p.k, p.v = y.data_ptr(), y.data_ptr() + C * es, y.data_ptr() + 2 * C * es
+    p.q_bs, p.q_ns, p.q_hs = y.stride(0), y.stride(1), D
+    if g.stride() != o.stride():
+        raise RuntimeError("packed_attention backward: dout and o layouts differ")
+    p.o, p.dout, p.o_bs, p.o_ns, p.o_hs = o.data_ptr(), g.data_ptr(), o.stride(0), o.stride(1), D
+    p.lse = lse.data_ptr()
+    p.dq, p.dk, p.dv = dy.data_ptr(), dy.data_ptr() + C * es, dy.data_ptr() + 2 * C * es
+    p.dq_bs, p.dq_ns, p.dq_hs = dy.stride(0), dy.stride(1), D
+    # per-batch column sums of dq | dk | dv, taken in the kernel: the qkv bias gradient rides on dy
+    # (LinearSK picks it up instead of a second pass over the (B*N, 3C) gradient)
+    dsum = torch.empty(Bsz, 3 * C, device=y.device, dtype=torch.float32)
+    p.dsum = dsum.data_ptr()
+    if words is None:
+        _lib.check(lib.mc_attn_bwd(p, _lib.stream_handle(y.device)), "mc_attn_bwd")
+    else:   # dk / dv of masked keys come back as stored zeros (dy is empty_like)
+        p.key_mask = words.data_ptr()
+        _lib.check(lib.mc_attn_masked_bwd(p, _lib.stream_handle(y.device)), "mc_attn_masked_bwd")
+    setattr(dy, COLSUM_ATTR, (sum_rows(dsum), dy._version))
+    return dy
+
+
 class PackedAttentionFn(torch.autograd.Function):
     """o = softmax(q k^T / sqrt(D)) v per head, for q / k / v the three C-wide slices of a packed
     (B, N, 3C) projection output (timm Attention's qkv Linear), o as (B, N, C) -- the layout
@@ -1608,61 +1675,56 @@ class PackedAttentionFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, heads):
-        Bsz, N, C3 = qkv.shape
-        C = C3 // 3
-        D = C // heads
-        if not (qkv.is_cuda and attn_supported(N, D, qkv.dtype)):
-            raise RuntimeError(f"packed_attention: unsupported (device {qkv.device}, N {N}, head_dim {D}, "
-                               f"{qkv.dtype}); bf16/f16 on the GPU, head_dim 64, N <= 256")
-        lib = _lib.load()
-        y = _hip_rows(qkv.reshape(Bsz * N, C3), 8, "packed_attention").view(Bsz, N, C3)
-        o = torch.empty(Bsz, N, C, device=qkv.device, dtype=qkv.dtype)
-        lse = torch.empty(Bsz, heads, N, device=qkv.device, dtype=torch.float32)
-        p = _lib.AttnFwdParams()
-        p.batch, p.heads, p.seqlen, p.head_dim, p.dtype = Bsz, heads, N, D, _lib.dtype_code(qkv.dtype)
-        p.scale = D ** -0.5
-        es = y.element_size()
-        p.q, p.k, p.v = y.data_ptr(), y.data_ptr() + C * es, y.data_ptr() + 2 * C * es
-        p.q_bs, p.q_ns, p.q_hs = y.stride(0), y.stride(1), D
-        p.o, p.o_bs, p.o_ns, p.o_hs = o.data_ptr(), o.stride(0), o.stride(1), D
-        p.lse = lse.data_ptr()
-        _lib.check(lib.mc_attn_fwd(p, _lib.stream_handle(qkv.device)), "mc_attn_fwd")
-        ctx.save_for_backward(y, o, lse)
-        ctx.heads = heads
-        return o
+        return _packed_attn_fwd(ctx, qkv, heads, None)
 
     @staticmethod
     def backward(ctx, go):
-        y, o, lse = ctx.saved_tensors
-        Bsz, N, C3 = y.shape
-        C = C3 // 3
-        D = C // ctx.heads
-        lib = _lib.load()
-        g = _hip_rows(go.to(o.dtype).reshape(Bsz * N, C), 8, "packed_attention backward").view(Bsz, N, C)
-        dy = torch.empty_like(y)
-        p = _lib.AttnBwdParams()
-        p.batch, p.heads, p.seqlen, p.head_dim, p.dtype = Bsz, ctx.heads, N, D, _lib.dtype_code(y.dtype)
-        p.scale = D ** -0.5
-        es = y.element_size()
-        p.q, p.k, p.v = y.data_ptr(), y.data_ptr() + C * es, y.data_ptr() + 2 * C * es
-        p.q_bs, p.q_ns, p.q_hs = y.stride(0), y.stride(1), D
-        if g.stride() != o.stride():
-            raise RuntimeError("packed_attention backward: dout and o layouts differ")
-        p.o, p.dout, p.o_bs, p.o_ns, p.o_hs = o.data_ptr(), g.data_ptr(), o.stride(0), o.stride(1), D
-        p.lse = lse.data_ptr()
-        p.dq, p.dk, p.dv = dy.data_ptr(), dy.data_ptr() + C * es, dy.data_ptr() + 2 * C * es
-        p.dq_bs, p.dq_ns, p.dq_hs = dy.stride(0), dy.stride(1), D
-        # per-batch column sums of dq | dk | dv, taken in the kernel: the qkv bias gradient rides on dy
-        # (LinearSK picks it up instead of a second pass over the (B*N, 3C) gradient)
-        dsum = torch.empty(Bsz, 3 * C, device=y.device, dtype=torch.float32)
-        p.dsum = dsum.data_ptr()
-        _lib.check(lib.mc_attn_bwd(p, _lib.stream_handle(y.device)), "mc_attn_bwd")
-        setattr(dy, COLSUM_ATTR, (sum_rows(dsum), dy._version))
-        return dy, None
+        return _packed_attn_bwd(ctx, go), None
 
 
-def packed_attention(qkv, heads):
-    return PackedAttentionFn.apply(qkv, heads)
+class PackedMaskedAttentionFn(torch.autograd.Function):
+    """PackedAttentionFn with a key-padding mask (HF attention_mask[:, None, None, :]): key_mask is
+    pack_key_mask's (B, 8) int32 bit words, one mask per batch row shared by heads and queries.
+    mc_attn_masked_fwd / _bwd: masked keys get probability 0 and zero dk / dv; padded query rows are
+    still computed."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads, key_mask):
+        Bsz = qkv.shape[0]
+        if not (key_mask.dtype == torch.int32 and key_mask.shape == (Bsz, _lib.MC_ATTN_MASK_WORDS)
+                and key_mask.device == qkv.device and key_mask.is_contiguous()):
+            raise RuntimeError(f"packed_attention: key_mask must be pack_key_mask's contiguous "
+                               f"({Bsz}, {_lib.MC_ATTN_MASK_WORDS}) int32 words on {qkv.device}, got "
+                               f"{tuple(key_mask.shape)} {key_mask.dtype} on {key_mask.device}")
+        return _packed_attn_fwd(ctx, qkv, heads, key_mask)
+
+    @staticmethod
+    def backward(ctx, go):
+        return _packed_attn_bwd(ctx, go), None, None
+
+
+def packed_attention(qkv, heads, key_mask=None):
+    """key_mask None: unmasked (PackedAttentionFn); else pack_key_mask(valid) words."""
+    if key_mask is None:
+        return PackedAttentionFn.apply(qkv, heads)
+    return PackedMaskedAttentionFn.apply(qkv, heads, key_mask)
+
+
+def pack_key_mask(valid):
+    """(B, N) bool, N <= 256 -> (B, 8) int32 on the same device: bit j of word t = valid[:, 32 t + j]
+    (the key_mask of mc_attn_masked_fwd / _bwd).  Torch ops only, no host sync; a tower packs once
+    per forward and hands the words to every layer."""
+    Bsz, N = valid.shape
+    W = _lib.MC_ATTN_MASK_WORDS
+    if N > 32 * W:
+        raise RuntimeError(f"pack_key_mask: {N} keys, at most {32 * W}")
+    bits = valid.to(torch.int64)
+    if N < 32 * W:
+        bits = torch.nn.functional.pad(bits, (0, 32 * W - N))
+    weights = torch.ones(32, dtype=torch.int64, device=valid.device) << torch.arange(32, device=valid.device)
+    words = (bits.view(Bsz, W, 32) * weights).sum(-1)            # [0, 2^32)
+    words = torch.where(words >= 2 ** 31, words - 2 ** 32, words)   # the same 32 bits as int32
+    return words.to(torch.int32).contiguous()
 
 
 # ---------------------------------------------------------------------------- SS2D cross-scan glue (mc_ss2d.h)
