@@ -145,6 +145,53 @@ size_t mc_ce_fused_fwd_workspace_bytes(int32_t M, int32_t N, int32_t with_column
 int mc_ce_fused_grad(const mc_ce_fused_params* p, void* stream);
 size_t mc_ce_fused_grad_workspace_bytes(int32_t M, int32_t N);
 
+/* Retrieval ranks of a whole evaluation set (no M x N matrix in memory).
+ * The reference's evaluate accumulates all image and text features and stops
+ * there: "all_image_features @ all_text_features will blow up memory and
+ * compute very quickly" (eval.py:65-66).  With S as above -- the similarity of
+ * ClipModel.get_logits (model.py:1104-1112),
+ *   S[i, j] = scale * sx[i] * sy[j] * sum_k X[i, k] Y[j, k]        (never stored)
+ * row i's label column is i + row_off and column j's label row is j + col_off:
+ *   gt_r[i] = #{ j != label(i), j < N : S[i, j] >  S[i, label(i)] }
+ *   eq_r[i] = #{ j != label(i), j < N : S[i, j] == S[i, label(i)] }
+ *   gt_c[j], eq_c[j] likewise down column j against S[label(j), j].
+ * The 0-based retrieval rank of the label is gt (ties for the model) to
+ * gt + eq (ties against it).  A row / column whose label falls outside the
+ * matrix gets gt = -1, eq = 0.  lse_r (M), lse_c (N) and *loss_out are those of
+ * mc_ce_fused_fwd with the same coef_r / coef_c.
+ * Two sweeps over the same 128 x 128 tiles: the fused forward's statistics
+ * sweep (which records the target logits), then a sweep whose epilogue
+ * compares every logit with its row and column target and counts; a fold
+ * kernel sums the per-tile counts in a fixed order (no atomics: repeated calls
+ * give identical bits).  Both sweeps run the same K loop and scale the
+ * accumulator with the same expression, so the target a logit is compared
+ * with has the bits the second sweep computes for that element; the label
+ * element itself is excluded by index, never by value.
+ * in_dtype: bf16 or fp32 (fp8: MC_ERR_DTYPE).  |row_off|, |col_off| < 2^30.
+ * Workspace: mc_retrieval_ranks_workspace_bytes, about
+ * 12 * (M * ceil(N/128) + N * ceil(M/128)) bytes, 16-B aligned. */
+typedef struct mc_retrieval_params {
+  int32_t M, N, K;
+  int32_t in_dtype;
+  const void* X; int64_t ldx;
+  const void* Y; int64_t ldy;
+  const float* row_scale_x;     /* sx, nullable */
+  const float* row_scale_y;     /* sy, nullable */
+  float scale;                  /* used when scale_dev == NULL */
+  const float* scale_dev;
+  int64_t row_off; float coef_r;
+  int64_t col_off; float coef_c;
+  int32_t* gt_r; int32_t* eq_r; /* out (M) */
+  int32_t* gt_c; int32_t* eq_c; /* out (N) */
+  float* lse_r;                 /* out (M) */
+  float* lse_c;                 /* out (N) */
+  float* loss_out;              /* device scalar */
+  void* workspace; size_t workspace_bytes;
+} mc_retrieval_params;
+
+int mc_retrieval_ranks(const mc_retrieval_params* p, void* stream);
+size_t mc_retrieval_ranks_workspace_bytes(int32_t M, int32_t N);
+
 #ifdef __cplusplus
 }
 #endif

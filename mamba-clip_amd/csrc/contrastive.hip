@@ -22,6 +22,13 @@
 //    partial reductions (no atomics).
 //  * ce_grad: fused softmax-minus-onehot gradient for the row and column CE
 //    terms in one pass, plus the logit_scale gradient sum(G*S)/scale.
+//  * retrieval ranks (mc_retrieval_ranks): the whole-set image <-> text ranks the
+//    reference's evaluate stops short of (eval.py:65-66: the n x n product of the
+//    accumulated features "will blow up memory"), for the similarity of
+//    ClipModel.get_logits (model.py:1104-1112).  The statistics sweep of the fused
+//    forward records each label's logit; a second sweep of the same tiles counts,
+//    per row and per column, the logits greater than / equal to it
+//    (rank_count_epilogue); rank_fold_kernel sums the tile counts.  No n x n buffer.
 #include <algorithm>
 #include <cstdlib>
 
@@ -64,6 +71,7 @@ struct GemmArgs {
   float2* rpart; float2* cpart;             // kEpi 1: (max, sumexp) partials [tiles_n][M], [tiles_m][N]
   float* tgt_r; float* tgt_c;               // kEpi 1: target logits (written by the tile holding them)
   float* gpart;                             // kEpi 2: per-workgroup sum(G * S), nullable
+  uint32_t* rcnt; uint32_t* ccnt;           // kEpi 3: packed (greater | equal << 16) counts [tiles_n][M], [tiles_m][N]
 };
 
 typedef uint8_t fp8_t;   // OCP e4m3fn bits
@@ -220,8 +228,92 @@ __device__ __forceinline__ void ce_stats_epilogue(const GemmArgs& g, f32x4 (&acc
   }
 }
 
+// Rank-count epilogue of mc_retrieval_ranks (second sweep): every in-range logit
+// of the tile is compared with its row's and its column's target logit, as the
+// statistics sweep recorded them (tr: the lane's 16 rows, tc: its 4 columns).
+// A count word packs "greater" in bits 0-15 and "equal" in bits 16-31: a tile
+// holds at most 128 candidates per row or column.  The label element is left
+// out by its diagonal index, never by value.  Reduction as in
+// ce_stats_epilogue: transpose-reduce inside the wave, the two waves sharing
+// rows / columns add through LDS, one word per row and tile column-block lands
+// in rcnt[tn][row] (ccnt[tm][col] likewise).  rank_fold_kernel sums them.
+__device__ __forceinline__ void rank_count_epilogue(const GemmArgs& g, const f32x4 (&acc)[4][4],
+                                                    const float (&row_scale)[4][4], const float (&col_scale)[4],
+                                                    float alpha, int row_base, int col_base, char* lds, int tm,
+                                                    int tn, int m0, int n0) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, wr = w >> 1, wc = w & 1;
+  const int dbase = col_base - row_base;   // col - row of acc[0][0][0]
+  float tc[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) tc[j] = col_base + j * 16 < g.N ? g.tgt_c[col_base + j * 16] : 0.f;
+  uint32_t rc[16], cc[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    float tr[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) tr[r] = row_base + i * 16 + r < g.M ? g.tgt_r[row_base + i * 16 + r] : 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      uint32_t cnt = 0u;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float v = (acc[i][j][r] * row_scale[i][r]) * (alpha * col_scale[j]);   // the bits of ce_stats_epilogue
+        const bool ok = (row_base + i * 16 + r < g.M) && (col_base + j * 16 < g.N);
+        const int d = dbase + 16 * (j - i) - r;
+        // a NaN compares neither greater nor equal: out-of-range and label elements count nowhere
+        const float vr = ok && d != g.off_r ? v : __builtin_nanf(""), vc = ok && d != -g.off_c ? v : __builtin_nanf("");
+        cnt += (vr > tr[r] ? 1u : 0u) + (vr == tr[r] ? 0x10000u : 0u);
+        cc[j] += (vc > tc[j] ? 1u : 0u) + (vc == tc[j] ? 0x10000u : 0u);
+      }
+      rc[4 * i + r] = cnt;
+    }
+    __builtin_amdgcn_sched_barrier(0);   // one 16-row block at a time: keeps the live compare masks few
+  }
+  // rows: 16 entries (k = 4i + r) per lane over its 4 columns, 4 exchange steps across the 16-lane group
+#pragma unroll
+  for (int st = 0; st < 4; ++st) {
+    const int o = 8 >> st;
+    const bool hi = (lane & o) != 0;
+#pragma unroll
+    for (int k = 0; k < o; ++k) {
+      const uint32_t send = hi ? rc[k] : rc[k + o], keep = hi ? rc[k + o] : rc[k];
+      rc[k] = keep + (uint32_t)__shfl_xor((int)send, o);
+    }
+  }
+  // lane holds row entry k = lane & 15; columns: 4 entries (j) per lane over its 16 rows, 2 exchange steps
+#pragma unroll
+  for (int st = 0; st < 2; ++st) {
+    const int o = 2 >> st, ol = 32 >> st;
+    const bool hi = (lane & ol) != 0;
+#pragma unroll
+    for (int k = 0; k < o; ++k) {
+      const uint32_t send = hi ? cc[k] : cc[k + o], keep = hi ? cc[k + o] : cc[k];
+      cc[k] = keep + (uint32_t)__shfl_xor((int)send, ol);
+    }
+  }
+  // lane holds column entry j = lane >> 4
+  uint32_t* rowp = reinterpret_cast<uint32_t*>(lds);       // [4 waves][64 rows]
+  uint32_t* colp = rowp + 4 * 64;                          // [4 waves][64 cols]
+  __syncthreads();                                         // main-loop LDS reads done
+  {
+    const int k = lane & 15;
+    rowp[w * 64 + (k >> 2) * 16 + 4 * (lane >> 4) + (k & 3)] = rc[0];
+    colp[w * 64 + (lane >> 4) * 16 + (lane & 15)] = cc[0];
+  }
+  __syncthreads();
+  if (wc == 0) {            // waves 0, 2: rows of their half, both column halves
+    const int row = m0 + wr * 64 + lane;
+    if (row < g.M) g.rcnt[(int64_t)tn * g.M + row] = rowp[w * 64 + lane] + rowp[(w + 1) * 64 + lane];
+  }
+  if (wr == 0) {            // waves 0, 1: columns of their half, both row halves
+    const int col = n0 + wc * 64 + lane;
+    if (col < g.N) g.ccnt[(int64_t)tm * g.N + col] = colp[w * 64 + lane] + colp[(w + 2) * 64 + lane];
+  }
+}
+
 // kEpi 0: C = alpha * sa * sb * A B^T.  kEpi 1 / 2: the same tile feeds a fused
 // softmax cross-entropy epilogue instead (statistics / gradient, see below).
+// kEpi 3: the rank-count epilogue above; the K loop is the one kEpi 1 runs.
 template <typename TIn, typename TOut, bool kAligned, int kEpi>
 __global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmArgs g) {
   constexpr int E = (int)sizeof(TIn);
@@ -391,6 +483,10 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmArgs g) {
   const int row_base = m0 + wr * 64 + 4 * (lane >> 4), col_base = n0 + wc * 64 + (lane & 15);
   if constexpr (kEpi == 1) {
     ce_stats_epilogue(g, acc, row_scale, col_scale, alpha, row_base, col_base, lds, tm, tn, m0, n0);
+    return;
+  }
+  if constexpr (kEpi == 3) {
+    rank_count_epilogue(g, acc, row_scale, col_scale, alpha, row_base, col_base, lds, tm, tn, m0, n0);
     return;
   }
   if constexpr (kEpi == 0) {
@@ -1030,6 +1126,34 @@ __global__ __launch_bounds__(256) void ce_fused_reduce_kernel(int M, int N, int 
   if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
 }
 
+// Folds the rank-count sweep's packed tile counts in tile order (no atomics): thread idx < M takes
+// row idx, the next N threads column idx - M.  A label outside the matrix gives gt = -1, eq = 0 (the
+// statistics sweep recorded no target there, so the counts of such a row mean nothing).
+__global__ __launch_bounds__(256) void rank_fold_kernel(int M, int N, int tiles_m, int tiles_n,
+                                                        const uint32_t* __restrict__ rcnt,
+                                                        const uint32_t* __restrict__ ccnt, int off_r, int off_c,
+                                                        int32_t* __restrict__ gt_r, int32_t* __restrict__ eq_r,
+                                                        int32_t* __restrict__ gt_c, int32_t* __restrict__ eq_c) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (int64_t)M + N) return;
+  const bool rows = t < M;
+  const int idx = rows ? (int)t : (int)(t - M);
+  const int n = rows ? M : N, other = rows ? N : M, parts = rows ? tiles_n : tiles_m;
+  const uint32_t* __restrict__ part = rows ? rcnt : ccnt;
+  const int64_t lab = (int64_t)idx + (rows ? off_r : off_c);
+  int32_t gt = -1, eq = 0;
+  if (lab >= 0 && lab < other) {
+    gt = 0;
+    for (int k = 0; k < parts; ++k) {
+      const uint32_t q = part[(int64_t)k * n + idx];
+      gt += (int32_t)(q & 0xFFFFu);
+      eq += (int32_t)(q >> 16);
+    }
+  }
+  (rows ? gt_r : gt_c)[idx] = gt;
+  (rows ? eq_r : eq_c)[idx] = eq;
+}
+
 // G = gout * (coef_r (softmax_r - onehot_r) + coef_c (softmax_c - onehot_c)); partial sum(G * S)
 template <typename TOut>
 __global__ __launch_bounds__(256) void ce_grad_kernel(int rows, int cols, const float* __restrict__ S, int64_t lds,
@@ -1419,5 +1543,79 @@ extern "C" int mc_ce_fused_grad(const mc_ce_fused_params* p, void* stream) {
                        p->scale_dev ? 1.f : 1.f / p->scale, p->scale_dev, p->dscale_out);
   const hipError_t e = hipGetLastError();
   MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "mc_ce_fused_grad: launch failed: %s", hipGetErrorString(e));
+  return MC_OK;
+}
+
+// ------------------------------------------------------------------ retrieval ranks (evaluation)
+namespace {
+struct RankWs {
+  FusedWs f;
+  uint32_t* rcnt; uint32_t* ccnt;
+  size_t bytes;
+};
+
+// the fused forward's workspace (column term on), then the packed tile counts
+RankWs rank_ws(int M, int N, void* base) {
+  const int tm = (M + BM - 1) / BM, tn = (N + BN - 1) / BN;
+  char* p = reinterpret_cast<char*>(base);
+  RankWs w;
+  w.f = fused_fwd_ws(M, N, true, base);
+  size_t off = w.f.bytes;
+  w.rcnt = reinterpret_cast<uint32_t*>(p + off); off += al16((size_t)tn * M * sizeof(uint32_t));
+  w.ccnt = reinterpret_cast<uint32_t*>(p + off); off += al16((size_t)tm * N * sizeof(uint32_t));
+  w.bytes = off;
+  return w;
+}
+}  // namespace
+
+extern "C" size_t mc_retrieval_ranks_workspace_bytes(int32_t M, int32_t N) {
+  if (M <= 0 || N <= 0) return 0;
+  return rank_ws(M, N, nullptr).bytes;
+}
+
+extern "C" int mc_retrieval_ranks(const mc_retrieval_params* p, void* stream) {
+  const char* who = "mc_retrieval_ranks";
+  MC_CHECK(p != nullptr, MC_ERR_INVALID, "%s: null params", who);
+  MC_CHECK(p->in_dtype == MC_DTYPE_BF16 || p->in_dtype == MC_DTYPE_F32, MC_ERR_DTYPE,
+           "%s: inputs must be bf16 or fp32", who);
+  GemmArgs g;
+  bool aligned;
+  const int rc = fill_operands(g, who, p->M, p->N, p->K, p->in_dtype, p->X, p->ldx, p->Y, p->ldy, aligned);
+  if (rc != MC_OK) return rc;
+  MC_CHECK(p->row_off > -(1 << 30) && p->row_off < (1 << 30) && p->col_off > -(1 << 30) && p->col_off < (1 << 30),
+           MC_ERR_SHAPE, "%s: label offsets out of range", who);
+  MC_CHECK(p->gt_r && p->eq_r && p->gt_c && p->eq_c && p->lse_r && p->lse_c && p->loss_out, MC_ERR_INVALID,
+           "%s: null output", who);
+  const RankWs w = rank_ws(p->M, p->N, p->workspace);
+  MC_CHECK(p->workspace && aligned16(p->workspace) && p->workspace_bytes >= w.bytes, MC_ERR_WORKSPACE,
+           "%s: workspace must be >= %zu bytes, 16-B aligned", who, w.bytes);
+  g.alpha = p->scale; g.alpha_dev = p->scale_dev;
+  g.sa = p->row_scale_x; g.sb = p->row_scale_y;
+  g.off_r = (int)p->row_off; g.off_c = (int)p->col_off;
+  g.coef_r = p->coef_r; g.coef_c = p->coef_c;
+  g.rpart = w.f.rpart; g.cpart = w.f.cpart; g.tgt_r = w.f.tgt_r; g.tgt_c = w.f.tgt_c;
+  g.rcnt = w.rcnt; g.ccnt = w.ccnt;
+  hipStream_t s = (hipStream_t)stream;
+  // sweep 1: statistics + target logits (exactly mc_ce_fused_fwd)
+  launch_gemm<1>(g, p->in_dtype, MC_DTYPE_F32, aligned, s);
+  const int nbr = (p->M + 255) / 256, nb = nbr + (p->N + 255) / 256;
+  hipLaunchKernelGGL(ce_fused_reduce_kernel, dim3(nb), dim3(256), 0, s, p->M, p->N, g.tiles_m, g.tiles_n, w.f.rpart,
+                     w.f.cpart, w.f.tgt_r, w.f.tgt_c, g.off_r, g.off_c, p->coef_r, p->coef_c, p->lse_r, p->lse_c, nbr,
+                     w.f.partial);
+  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, w.f.partial, nb, 1.f, nullptr, p->loss_out);
+  // sweep 2: the same tiles against the recorded targets, then the fold
+  const dim3 grid(g.tiles_m * g.tiles_n), block(256);
+  if (p->in_dtype == MC_DTYPE_BF16) {
+    if (aligned) hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, float, true, 3>), grid, block, 0, s, g);
+    else hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, float, false, 3>), grid, block, 0, s, g);
+  } else {
+    if (aligned) hipLaunchKernelGGL((gemm_nt_kernel<float, float, true, 3>), grid, block, 0, s, g);
+    else hipLaunchKernelGGL((gemm_nt_kernel<float, float, false, 3>), grid, block, 0, s, g);
+  }
+  const int nf = (int)(((int64_t)p->M + p->N + 255) / 256);
+  hipLaunchKernelGGL(rank_fold_kernel, dim3(nf), dim3(256), 0, s, p->M, p->N, g.tiles_m, g.tiles_n, w.rcnt, w.ccnt,
+                     g.off_r, g.off_c, p->gt_r, p->eq_r, p->gt_c, p->eq_c);
+  const hipError_t e = hipGetLastError();
+  MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e));
   return MC_OK;
 }

@@ -134,6 +134,20 @@ class CEFusedParams(ctypes.Structure):
     ]
 
 
+class RetrievalParams(ctypes.Structure):
+    """Mirror of ``mc_retrieval_params`` (include/mc_contrastive.h)."""
+    _fields_ = [
+        ("M", c_i32), ("N", c_i32), ("K", c_i32), ("in_dtype", c_i32),
+        ("X", c_vp), ("ldx", c_i64), ("Y", c_vp), ("ldy", c_i64),
+        ("row_scale_x", c_fp), ("row_scale_y", c_fp),
+        ("scale", ctypes.c_float), ("scale_dev", c_fp),
+        ("row_off", c_i64), ("coef_r", ctypes.c_float), ("col_off", c_i64), ("coef_c", ctypes.c_float),
+        ("gt_r", c_vp), ("eq_r", c_vp), ("gt_c", c_vp), ("eq_c", c_vp),
+        ("lse_r", c_fp), ("lse_c", c_fp), ("loss_out", c_fp),
+        ("workspace", c_vp), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
 class QkvPackParams(ctypes.Structure):
     """Mirror of ``mc_qkv_pack_params`` (include/mc_ops.h)."""
     _fields_ = [
@@ -294,6 +308,8 @@ SYMBOLS = {
     "mc_ce_fused_fwd_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32]),
     "mc_ce_fused_grad": (ctypes.c_int, [ctypes.POINTER(CEFusedParams), c_vp]),
     "mc_ce_fused_grad_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32]),
+    "mc_retrieval_ranks": (ctypes.c_int, [ctypes.POINTER(RetrievalParams), c_vp]),
+    "mc_retrieval_ranks_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32]),
     "mc_add_rmsnorm_fwd": (ctypes.c_int, [c_i32, c_i32, c_i32, c_vp, c_fp, c_fp, ctypes.c_float, c_vp, c_fp, c_fp,
                                           c_vp]),
     "mc_add_rmsnorm_bwd": (ctypes.c_int, [c_i32, c_i32, c_i32, c_vp, c_fp, c_fp, c_fp, c_fp, c_vp, c_fp, c_fp, c_vp,

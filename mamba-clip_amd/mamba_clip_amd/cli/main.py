@@ -68,6 +68,10 @@ def build_parser():
     p.add_argument("--grad-clip-norm", type=float, default=None)
     p.add_argument("--log-every-n-steps", type=int, default=10)
     p.add_argument("--benchmark", action="store_true", help="print one JSON throughput line at the end")
+    p.add_argument("--val-frequency", type=int, default=0,
+                   help="evaluate every this many epochs and after the last one (0: never)")
+    p.add_argument("--val-num-samples", type=int, default=None,
+                   help="validation samples (synthetic: distinct batches; default 4 batches)")
     return p
 
 
@@ -135,24 +139,41 @@ def main(argv=None):
     n_batches = max(1, (args.train_num_samples or 16 * args.batch_size) // args.batch_size)
     img_size = getattr(inner.visual, "patch_embed", None)
     img_size = img_size.grid * img_size.patch if img_size is not None else 224
+    val_batches = 0
+    if args.val_frequency:
+        val_batches = max(1, (args.val_num_samples or 4 * args.batch_size) // args.batch_size)
     data = get_synthetic_data(args.batch_size, n_batches, img_size, text.context_length, text.vocab_size, device,
                               seed=1000 + args.rank, balanced=args.balanced_mixup is not None,
-                              num_classes=args.num_classes)
+                              num_classes=args.num_classes, val_batches=val_batches)
     total_steps = n_batches // args.accum_freq * args.epochs
     scheduler = _make_scheduler(optimizer, args, total_steps)
 
+    val_metrics, val_seconds = {}, 0.0
     t0 = time.time()
     for epoch in range(args.epochs):
         metrics = train_one_epoch(model, data, loss, epoch, optimizer, scaler, scheduler, args)
+        if args.val_frequency:                 # evaluation (eval.py:47-178) stays out of the timed training region
+            from ..eval import evaluate
+            if device.type == "cuda":
+                torch.cuda.synchronize(device)
+            tv = time.time()
+            m = evaluate(model, data, epoch + 1, args)
+            if m:
+                val_metrics = m
+                logging.info(f"validation after epoch {epoch + 1}: {m}")
+            val_seconds += time.time() - tv
     if device.type == "cuda":
         torch.cuda.synchronize(device)
-    elapsed = time.time() - t0
+    elapsed = time.time() - t0 - val_seconds
     if is_master(args):
         pairs = args.batch_size * n_batches * args.epochs * args.world_size
         logging.info(f"done: {pairs} pairs in {elapsed:.2f} s ({pairs / elapsed:.1f} pairs/s); {metrics}")
         if args.benchmark:
-            print(json.dumps({"pairs_per_sec": pairs / elapsed, "seconds": elapsed, "world_size": args.world_size,
-                              "final": {k: (v if math.isfinite(v) else None) for k, v in metrics.items()}}))
+            result = {"pairs_per_sec": pairs / elapsed, "seconds": elapsed, "world_size": args.world_size,
+                      "final": {k: (v if math.isfinite(v) else None) for k, v in metrics.items()}}
+            if val_metrics:
+                result["val"] = {k: (v if math.isfinite(v) else None) for k, v in val_metrics.items()}
+            print(json.dumps(result))
     return 0
 
 

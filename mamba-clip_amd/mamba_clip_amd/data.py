@@ -38,15 +38,25 @@ class _SyntheticLoader:
     the ComboLoader pair (batch, balanced batch) that --balanced-mixup consumes
     (reference data.py:218-239, train.py:131-151)."""
 
-    def __init__(self, batch, num_batches, balanced=False, **kw):
+    def __init__(self, batch, num_batches, balanced=False, distinct=False, **kw):
         self.batch, self.num_batches, self.kw, self.balanced = batch, num_batches, kw, balanced
         self.num_samples = batch * num_batches
         self._cached = None
+        self.distinct = distinct
 
     def __len__(self):
         return self.num_batches
 
     def __iter__(self):
+        if self.distinct:
+            # one seed per batch (validation: a repeated batch would make every pair a duplicate);
+            # generated once, then resident like the repeated batch
+            if self._cached is None:
+                seed = self.kw.get("seed", 0)
+                self._cached = [synthetic_batch(self.batch, **dict(self.kw, seed=seed + i))
+                                for i in range(self.num_batches)]
+            yield from self._cached
+            return
         if self._cached is None:
             b = synthetic_batch(self.batch, **self.kw)
             if self.balanced:
@@ -69,11 +79,16 @@ class DataInfo:
 
 
 def get_synthetic_data(batch, num_batches, image_size, context_length, vocab_size, device, seed=0,
-                       image_dtype=torch.float32, balanced=False, num_classes=2):
-    loader = _SyntheticLoader(batch, num_batches, balanced=balanced, image_size=image_size,
-                              context_length=context_length, vocab_size=vocab_size, num_classes=num_classes,
-                              device=device, seed=seed, image_dtype=image_dtype)
-    return {"train": DataInfo(loader)}
+                       image_dtype=torch.float32, balanced=False, num_classes=2, val_batches=0, val_seed=None):
+    """{"train": DataInfo}; with val_batches > 0 also {"val": DataInfo} of that many DISTINCT batches
+    (seeds val_seed + i, default seed + 500000 + i)."""
+    kw = dict(image_size=image_size, context_length=context_length, vocab_size=vocab_size, num_classes=num_classes,
+              device=device, image_dtype=image_dtype)
+    data = {"train": DataInfo(_SyntheticLoader(batch, num_batches, balanced=balanced, seed=seed, **kw))}
+    if val_batches > 0:
+        vs = seed + 500000 if val_seed is None else val_seed
+        data["val"] = DataInfo(_SyntheticLoader(batch, val_batches, distinct=True, seed=vs, **kw))
+    return data
 
 
 def normalize_images(img_u8, mean=None, std=None):

@@ -10,8 +10,12 @@
                           the logits never exist in memory (mc_ce_fused_*).
 ``ce_stats`` / ``ce_grad`` the unfused statistics / gradient kernels over a
                           materialised S (kept for logits the caller needs anyway).
+``retrieval_ranks(X, Y, scale)``  evaluation: per-row / per-column counts of logits that beat or
+                          tie the label's, plus LSE and loss, again without the logits in
+                          memory (mc_retrieval_ranks).
 All launches go on the current HIP stream; nothing synchronises.
 """
+import collections
 import ctypes
 import os
 import weakref
@@ -210,6 +214,92 @@ def ce_fused_grad(X, Y, sc, lse_r, lse_c, row_off, coef_r, col_off, coef_c, gout
         p.dscale_out, p.workspace, p.workspace_bytes = dscale.data_ptr(), ws.data_ptr(), ws_b
     _lib.check(lib.mc_ce_fused_grad(p, _lib.stream_handle(X.device)), "mc_ce_fused_grad")
     return G, dscale
+
+
+RetrievalRanks = collections.namedtuple("RetrievalRanks", "gt_r eq_r gt_c eq_c lse_r lse_c loss")
+
+
+def _retrieval_ranks_dense(X, Y, scale, row_off, col_off):
+    """retrieval_ranks on host tensors: the same quantities from the dense fp64 logits."""
+    M, N = X.shape[0], Y.shape[0]
+    S = float(scale) * (X.double() @ Y.double().t())
+
+    def side(S, off):
+        n, other = S.shape
+        lab = torch.arange(n) + off
+        ok = (lab >= 0) & (lab < other)
+        labc = lab.clamp(0, other - 1)
+        t = S.gather(1, labc[:, None])
+        notlab = torch.ones_like(S, dtype=torch.bool)
+        notlab[torch.arange(n), labc] = False
+        gt = ((S > t) & notlab).sum(1).to(torch.int32)
+        eq = ((S == t) & notlab).sum(1).to(torch.int32)
+        gt = torch.where(ok, gt, torch.full_like(gt, -1))
+        eq = torch.where(ok, eq, torch.zeros_like(eq))
+        lse = torch.logsumexp(S, dim=1)
+        nll = lse - torch.where(ok, t[:, 0], torch.zeros_like(lse))
+        return gt, eq, lse, nll.sum()
+
+    gt_r, eq_r, lse_r, nr = side(S, int(row_off))
+    gt_c, eq_c, lse_c, nc = side(S.t(), int(col_off))
+    loss = (0.5 / M) * nr + (0.5 / N) * nc
+    return RetrievalRanks(gt_r, eq_r, gt_c, eq_c, lse_r.float(), lse_c.float(), loss.float())
+
+
+def retrieval_ranks(X, Y, scale, row_off=0, col_off=0):
+    """Whole-set retrieval ranks of S = scale * X @ Y^T without storing S (mc_retrieval_ranks).
+
+    Row i's label is column i + row_off, column j's label is row j + col_off.  Returns
+    ``RetrievalRanks(gt_r, eq_r, gt_c, eq_c, lse_r, lse_c, loss)``: int32 counts of the other
+    logits of a row (column) strictly greater than / equal to its label's logit (gt = -1, eq = 0
+    where the label falls outside S), the fp32 log-sum-exp of every row and column, and
+    loss = (sum_i CE_row_i / M + sum_j CE_col_j / N) / 2 -- the CLIP loss of the whole set when
+    M == N.  X, Y: 2-D, K contiguous, both bf16 or both fp32; ``scale`` a float or a device
+    scalar tensor (read on the device: no host sync).  Host tensors take a dense torch path."""
+    if not (torch.is_tensor(X) and torch.is_tensor(Y)) or X.dim() != 2 or Y.dim() != 2:
+        raise ValueError("retrieval_ranks: X and Y must be 2-D tensors")
+    if X.dtype != Y.dtype or X.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError("retrieval_ranks: X and Y must both be bf16 or both fp32")
+    if X.shape[1] != Y.shape[1]:
+        raise ValueError("retrieval_ranks: inner dimensions differ")
+    if X.shape[0] == 0 or Y.shape[0] == 0:
+        raise ValueError("retrieval_ranks: empty operand")
+    if (X.shape[1] > 1 and X.stride(1) != 1) or (Y.shape[1] > 1 and Y.stride(1) != 1):
+        raise ValueError("retrieval_ranks: X and Y must have K contiguous")
+    if X.device != Y.device:
+        raise ValueError("retrieval_ranks: X and Y must be on the same device")
+    if not -(1 << 30) < int(row_off) < (1 << 30) or not -(1 << 30) < int(col_off) < (1 << 30):
+        raise ValueError("retrieval_ranks: label offsets must satisfy |off| < 2^30")
+    if torch.is_tensor(scale) and scale.numel() != 1:
+        raise ValueError("retrieval_ranks: scale must be a scalar")
+    if not X.is_cuda:
+        return _retrieval_ranks_dense(X, Y, scale, row_off, col_off)
+    lib = _lib.load()
+    M, N = X.shape[0], Y.shape[0]
+    dev = X.device
+    counts = torch.empty(2 * (M + N), device=dev, dtype=torch.int32)
+    gt_r, eq_r, gt_c, eq_c = counts[:M], counts[M:2 * M], counts[2 * M:2 * M + N], counts[2 * M + N:]
+    lse = torch.empty(M + N, device=dev, dtype=torch.float32)
+    lse_r, lse_c = lse[:M], lse[M:]
+    loss = torch.empty((), device=dev, dtype=torch.float32)
+    p = _lib.RetrievalParams()
+    p.M, p.N, p.K = M, N, X.shape[1]
+    p.in_dtype = _lib.dtype_code(X.dtype)
+    p.X, p.ldx, p.Y, p.ldy = X.data_ptr(), X.stride(0), Y.data_ptr(), Y.stride(0)
+    sc = None
+    if torch.is_tensor(scale):
+        sc = scale.detach().reshape(()).to(device=dev, dtype=torch.float32).contiguous()
+        p.scale_dev = sc.data_ptr()
+    else:
+        p.scale = float(scale)
+    p.row_off, p.coef_r, p.col_off, p.coef_c = int(row_off), 0.5 / M, int(col_off), 0.5 / N
+    p.gt_r, p.eq_r, p.gt_c, p.eq_c = gt_r.data_ptr(), eq_r.data_ptr(), gt_c.data_ptr(), eq_c.data_ptr()
+    p.lse_r, p.lse_c, p.loss_out = lse_r.data_ptr(), lse_c.data_ptr(), loss.data_ptr()
+    ws_b = lib.mc_retrieval_ranks_workspace_bytes(M, N)
+    ws = _ws(ws_b, dev)
+    p.workspace, p.workspace_bytes = ws.data_ptr(), ws_b
+    _lib.check(lib.mc_retrieval_ranks(p, _lib.stream_handle(dev)), "mc_retrieval_ranks")
+    return RetrievalRanks(gt_r, eq_r, gt_c, eq_c, lse_r, lse_c, loss)
 
 
 def _mm_nt(a, b_t, out):
