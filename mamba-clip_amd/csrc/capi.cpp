@@ -22,4 +22,4 @@ const char* last_error() { return g_last_error.c_str(); }
 }  // namespace mc
 
 extern "C" const char* mc_last_error(void) { return mc::last_error(); }
-extern "C" const char* mc_version(void) { return "mamba_clip_amd 0.1.0 (gfx950)"; }
+extern "C" const char* mc_version(void) { return "mamba_clip_amd 0.2.0 (gfx950)"; }

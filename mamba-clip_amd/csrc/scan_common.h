@@ -344,8 +344,7 @@ __device__ __forceinline__ f32x2 silu2(f32x2 z) {
   return z * f32x2{fast_rcp(ep.x), fast_rcp(ep.y)};
 }
 
-// Forward kernel arguments (scan_fwd.hip, scan_fwd_pair.hip).
-// MFMA operand vectors of the projected-delta tile (4 16-bit values per lane)
+// MFMA operand vectors of a 16x16x16 tile (4 16-bit values per lane; mixer_proj.hip)
 template <typename TI> struct Mfma16;
 template <> struct Mfma16<bf16_t> {
   typedef short v4 __attribute__((ext_vector_type(4)));
@@ -356,6 +355,7 @@ template <> struct Mfma16<f16_t> {
   static __device__ __forceinline__ f32x4 mma(v4 a, v4 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0); }
 };
 
+// Forward kernel arguments (scan_fwd.hip, scan_fwd_pair.hip).
 struct FwdArgs {
   int batch, dim, seqlen, dstate, n_groups, n_chunks, n_states, nblk, total_blocks;
   int softplus;
@@ -365,10 +365,6 @@ struct FwdArgs {
   void* out; float* chunk_states; float* last_state;
   void* out_y; int64_t y_bs, y_ds;   // nullable: pre-gate y + D u (training with z: the backward's dz input)
   int rev_groups, u_groups;          // grouped directions (0 = off; element-wise path only)
-  // projected delta (pair kernel only): delta = dpw (dim x rank) . dpx^T, formed per chunk on MFMA
-  const void* dpx; const void* dpw; int rank;
-  int64_t dpx_bs, dpx_ts, dpw_ds;
-  void* delta_out;                   // nullable: the formed delta, strides dt_bs / dt_ds
   // B / C rows as given (the pair kernel reads them directly; the others read the relaid bct)
   const void* B; const void* C;
   int64_t B_bs, B_gs, B_ns, C_bs, C_gs, C_ns;

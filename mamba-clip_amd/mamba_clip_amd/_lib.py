@@ -40,9 +40,7 @@ class ScanFwdParams(ctypes.Structure):
         ("workspace", c_vp), ("workspace_bytes", ctypes.c_size_t),
         ("out_y", c_vp), ("out_y_batch_stride", c_i64), ("out_y_dim_stride", c_i64),
         ("reverse_groups", c_i32), ("u_groups", c_i32),
-        ("delta_proj_x", c_vp), ("delta_proj_w", c_vp), ("delta_rank", c_i32),
-        ("dpx_batch_stride", c_i64), ("dpx_token_stride", c_i64), ("dpw_dim_stride", c_i64),
-        ("delta_out", c_vp), ("state_interval", c_i32),
+        ("state_interval", c_i32),
     ]
 
 
@@ -65,10 +63,7 @@ class ScanBwdParams(ctypes.Structure):
         ("du", c_vp), ("ddelta", c_vp), ("dz", c_vp), ("dB", c_vp), ("dC", c_vp),
         ("dA", c_fp), ("dD", c_fp), ("ddelta_bias", c_fp),
         ("workspace", c_vp), ("workspace_bytes", ctypes.c_size_t),
-        ("out_y", c_vp), ("out_y_batch_stride", c_i64), ("out_y_dim_stride", c_i64),
         ("reverse_groups", c_i32), ("u_groups", c_i32),
-        ("delta_proj_x", c_vp), ("delta_proj_w", c_vp), ("delta_rank", c_i32),
-        ("dpx_batch_stride", c_i64), ("dpx_token_stride", c_i64), ("dpw_dim_stride", c_i64),
         ("state_interval", c_i32),
         ("dB_batch_stride", c_i64), ("dB_group_stride", c_i64), ("dB_dstate_stride", c_i64),
         ("dC_batch_stride", c_i64), ("dC_group_stride", c_i64), ("dC_dstate_stride", c_i64),

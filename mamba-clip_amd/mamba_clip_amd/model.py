@@ -37,9 +37,8 @@ from .ops import (GradHandoff, GradSlab, _compute_dtype, add_layernorm, add_pos,
                   causal_conv1d, l2_normalize, linear_sk, mixer_proj, mixer_proj_ok, mlp, neg_exp_many,
                   pack_key_mask, packed_attention, patch_im2col, qkv_proj, split_rows, split_rows_n, ss2d_conv_stack,
                   ss2d_merge_ln_gate, ss2d_proj, ss2d_proj_ok, token_embed, weight_cast_scope, wleft_mm)
-from .selective_scan_interface import (SS2D_REVERSE_GROUPS, SS2D_U_GROUPS, ProjectedScanFn, SelectiveScanFn,
-                                       fine_state_scope,
-                                       grouped_scan_fn, projected_scan_ok, selective_scan_fn)
+from .selective_scan_interface import (SS2D_REVERSE_GROUPS, SS2D_U_GROUPS, SelectiveScanFn, fine_state_scope,
+                                       grouped_scan_fn, selective_scan_fn)
 
 
 # ============================================================================ Mamba text tower
@@ -90,10 +89,6 @@ class MambaMixer(nn.Module):
         self.D = nn.Parameter(torch.ones(self.d_inner))
         self.D._no_weight_decay = True
         self.out_proj = nn.Linear(self.d_inner, d_model, bias=False)
-        # dt_proj inside the scan (ProjectedScanFn) where the shapes allow.  Off by default: the scan
-        # kernels are VALU-bound, so forming delta on their MFMAs costs more than the delta stream it
-        # saves (C2 step 88.4 vs 86.5 ms on one box, profiles/r03/c2_ab_fuse_dt_proj.txt)
-        self.fuse_dt_proj = os.environ.get("MAMBA_CLIP_AMD_FUSE_DT_PROJ", "0") == "1"   # A/B toggle
         self.du_handoff = True   # scan du -> x_proj's dX epilogue (ops.GradHandoff)
         # x_proj + dt_proj as one HIP pass each way (ops.MixerProjFn); A/B toggle
         self.fuse_proj = os.environ.get("MAMBA_CLIP_AMD_FUSE_MIXER_PROJ", "0") == "1"
@@ -116,16 +111,7 @@ class MambaMixer(nn.Module):
         if A is None:
             A = -torch.exp(self.A_log.float())
         dz = (slab, di) if slab is not None else None
-        if self.fuse_dt_proj and projected_scan_ok(x, R, N):
-            # dt_proj inside the scan (ProjectedScanFn): x_proj's dt rows come out token-major,
-            # (B*L, R), the scan kernel forms delta per chunk on MFMA; B / C stay channel-major
-            dt_raw = linear_sk(x_cm.t(), self.x_proj.weight[:R])              # (B*L, R)
-            BC = wleft_mm(self.x_proj.weight[R:], x_cm)                       # (2N, B*L)
-            Bm = BC[:N].view(N, Bsz, L).transpose(0, 1)
-            Cm = BC[N:].view(N, Bsz, L).transpose(0, 1)
-            y = ProjectedScanFn.apply(x, dt_raw, self.dt_proj.weight, A, Bm, Cm, self.D.float(), z,
-                                      self.dt_proj.bias.float(), True, dz)
-        elif self.fuse_proj and mixer_proj_ok(x_cm, R, N):
+        if self.fuse_proj and mixer_proj_ok(x_cm, R, N):
             # x_proj and dt_proj in one pass over x (and one backward pass over ddelta that also adds
             # the scan's du into dx: ops.GradHandoff)
             hand = GradHandoff() if (self.du_handoff and x.requires_grad) else None

@@ -47,7 +47,7 @@ def test_scan_pair_kernels_have_no_packed_opsel_high_broadcast(src, tmp_path):
     assert spills, "no kernel metadata found"
     if src == "scan_fwd_pair.hip":
         hot = {k: v for k, v in spills.items() if "scan_fwd_pair_kernel" in k}
-    else:   # <TI, softplus, z, projected delta, fine>: the fine instances end in Lb1EEE
+    else:   # <TI, softplus, z, fine>: the fine instances end in Lb1EEE
         hot = {k: v for k, v in spills.items() if "scan_bwd_pair_kernel" in k and k.endswith("Lb1EEEvNS0_11BwdPairArgsE")}
     assert hot, sorted(spills)[:4]
     assert all(v == 0 for v in hot.values()), {k: v for k, v in hot.items() if v}

@@ -1,6 +1,6 @@
 """Dev tool: interleaved same-box A/B of the C2 training step with a model toggle (not the bench contract).
 
-usage: python tools/ab_step.py --toggle fuse_dt_proj [--model vit_b16-mamba130m --batch 256 --steps 10 --reps 3]
+usage: python tools/ab_step.py --toggle du_handoff [--model vit_b16-mamba130m --batch 256 --steps 10 --reps 3]
 The toggle is an attribute set on every module that has it (True = variant A, False = variant B), or
 `ops.NAME` / `train.NAME` for a module-level flag of mamba_clip_amd.ops / .train.
 """
@@ -25,7 +25,7 @@ ap.add_argument("--model", default="vit_b16-mamba130m")
 ap.add_argument("--batch", type=int, default=256)
 ap.add_argument("--steps", type=int, default=10)
 ap.add_argument("--reps", type=int, default=3)
-ap.add_argument("--toggle", default="fuse_dt_proj")
+ap.add_argument("--toggle", required=True)
 ap.add_argument("--watchdog", type=float, default=0, help="dump every thread's stack and exit after S seconds")
 args = ap.parse_args()
 if args.watchdog:
