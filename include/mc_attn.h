@@ -15,6 +15,12 @@
  * projection output and o / dq / dk / dv can be written straight into the layouts the
  * next GEMM reads.  Requirements: head_dim == 64, 1 <= seqlen <= 256, dtype bf16 or f16,
  * 16-B aligned rows (pointers and the three strides multiples of 8 elements).
+ * Batch and head strides are 64-bit and free (any sign, any size).  Token strides are not: the
+ * kernels read K / V (every kernel) and, backward at seqlen > 224, Q / dO / O through 32-bit
+ * buffer byte offsets, so q_ns (all four entry points) and o_ns (the two backward ones) must be
+ * >= 0 with ((seqlen - 1) * ns + 64) * 2 bytes <= 2^31 -- at seqlen 256 ns <= 4210752 elements;
+ * anything else returns MC_ERR_SHAPE before a launch.  (o_ns of the forward and dq_ns are only
+ * written through, with 64-bit addresses: no limit.)
  * Same conventions as mc_scan.h: device pointers, asynchronous on `stream`,
  * MC_OK / MC_ERR_* return codes.
  */

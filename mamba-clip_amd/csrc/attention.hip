@@ -673,6 +673,17 @@ static int check_common(int B, int H, int N, int D, int dtype, const char* who) 
   MC_CHECK(dtype == MC_DTYPE_BF16 || dtype == MC_DTYPE_F16, MC_ERR_DTYPE, "%s: dtype %d (bf16 / f16 only)", who, dtype);
   return MC_OK;
 }
+// The kernels address K / V (every kernel) and, in the N > 224 backward, Q / dO / O through 32-bit
+// buffer byte offsets n * ns * sizeof(T) under a range of ((N - 1) * ns + 64) * sizeof(T) bytes, with
+// offset 0x80000000 as the "reads zero" row past N: beyond 2^31 bytes the offsets wrap and the
+// sentinel falls inside the range.  N and the dtype (16-bit) are already validated.
+static int check_token_stride(int64_t ns, int N, const char* who, const char* name) {
+  const int64_t es = 2;   // bf16 / f16
+  MC_CHECK(ns >= 0 && ns <= INT64_MAX / (2 * MC_ATTN_MAX_SEQ) && ((int64_t)(N - 1) * ns + kD) * es <= ((int64_t)1 << 31),
+           MC_ERR_SHAPE, "%s: token stride %s = %lld: negative, or ((seqlen - 1) * %s + %d) * %d bytes exceed 2^31 (32-bit buffer offsets)",
+           who, name, (long long)ns, name, kD, (int)es);
+  return MC_OK;
+}
 
 }  // namespace attn
 }  // namespace mc
@@ -688,6 +699,7 @@ static int run_fwd(const P* p, A& a, void* stream, const char* who) {
   MC_CHECK(attn::rows_ok(p->q, p->q_bs, p->q_ns, p->q_hs) && attn::rows_ok(p->k, p->q_bs, p->q_ns, p->q_hs) &&
                attn::rows_ok(p->v, p->q_bs, p->q_ns, p->q_hs) && attn::rows_ok(p->o, p->o_bs, p->o_ns, p->o_hs) && p->lse,
            MC_ERR_INVALID, "%s: q / k / v / o need 16-B aligned rows (strides %% 8 elements), lse non-null", who);
+  if (const int rs = attn::check_token_stride(p->q_ns, p->seqlen, who, "q_ns"); rs != MC_OK) return rs;
   if constexpr (std::is_same<A, attn::FwdArgsM>::value) {
     MC_CHECK(p->key_mask && ((uintptr_t)p->key_mask & 3) == 0, MC_ERR_INVALID, "%s: key_mask null or not 4-B aligned", who);
     a.mask = p->key_mask;
@@ -717,6 +729,8 @@ static int run_bwd(const P* p, A& a, void* stream, const char* who) {
                attn::rows_ok(p->dk, p->dq_bs, p->dq_ns, p->dq_hs) && attn::rows_ok(p->dv, p->dq_bs, p->dq_ns, p->dq_hs) &&
                p->lse,
            MC_ERR_INVALID, "%s: every tensor needs 16-B aligned rows (strides %% 8 elements), lse non-null", who);
+  if (const int rs = attn::check_token_stride(p->q_ns, p->seqlen, who, "q_ns"); rs != MC_OK) return rs;
+  if (const int rs = attn::check_token_stride(p->o_ns, p->seqlen, who, "o_ns"); rs != MC_OK) return rs;
   if constexpr (std::is_same<A, attn::BwdArgsM>::value) {
     MC_CHECK(p->key_mask && ((uintptr_t)p->key_mask & 3) == 0, MC_ERR_INVALID, "%s: key_mask null or not 4-B aligned", who);
     a.mask = p->key_mask;
