@@ -35,12 +35,6 @@
 #include "mc_common.h"
 #include "../../include/mc_contrastive.h"
 
-#ifndef MC_SIM_EXP
-#define MC_SIM_EXP 0
-#endif
-#ifndef MC_NT_STORE
-#define MC_NT_STORE 0
-#endif
 namespace mc {
 namespace ctr {
 
@@ -75,11 +69,6 @@ struct GemmArgs {
 };
 
 typedef uint8_t fp8_t;   // OCP e4m3fn bits
-
-__device__ __forceinline__ int xcd_remap(int bid, int nblocks) {
-  const int xcd = bid & 7, q = nblocks >> 3, r = nblocks & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-}
 
 __device__ __forceinline__ void lse_merge(float& m, float& s, float m2, float s2) {
   const float mm = fmaxf(m, m2);
@@ -566,11 +555,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmArgs g) {
         const int row = m0 + wr * 64 + p * 32 + row_l, col = n0 + wc * 64 + c4;
         TOut* dst = C + (int64_t)row * g.ldc + col;
         if (full) {
-#if MC_NT_STORE
-          __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(dst));   // streamed: nothing re-reads it here
-#else
           *reinterpret_cast<f32x4*>(dst) = v;
-#endif
         } else if (row < g.M) {
 #pragma unroll
           for (int e = 0; e < 4; ++e)
@@ -591,11 +576,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmArgs g) {
                               bits16<TOut>(v0[2]) | (bits16<TOut>(v0[3]) << 16),
                               bits16<TOut>(v1[0]) | (bits16<TOut>(v1[1]) << 16),
                               bits16<TOut>(v1[2]) | (bits16<TOut>(v1[3]) << 16)};
-#if MC_NT_STORE
-          __builtin_nontemporal_store(pk, reinterpret_cast<u32x4_t*>(dst));
-#else
           *reinterpret_cast<u32x4_t*>(dst) = pk;
-#endif
         } else if (row < g.M) {
 #pragma unroll
           for (int e = 0; e < 8; ++e)
@@ -691,11 +672,7 @@ __global__ __launch_bounds__(256, 2) void sim_fp8_kernel(const GemmArgs g) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-#if MC_SIM_EXP == 2
-  const int nk = 0;
-#else
   const int nk = g.K / kSBK;
-#endif
   if (nk > 0) issue(0);
   if (nk > 1) issue(1);
   // fragment read offsets: lane row (l & 15) of a 16-row tile, K bytes [32 (l >> 4), +32) = chunks 2g, 2g + 1
@@ -758,9 +735,6 @@ __global__ __launch_bounds__(256, 2) void sim_fp8_kernel(const GemmArgs g) {
         const f32x4 v = *reinterpret_cast<const f32x4*>(ep + row_l * kEpStride + c4);
         const int row = m0 + wr * 64 + p * 32 + row_l, col = n0 + wc * 64 + c4;
         TOut* dst = C + (int64_t)row * g.ldc + col;
-#if MC_SIM_EXP == 1
-        if (v[0] == 1234.5f) *reinterpret_cast<f32x4*>(dst) = v;
-#else
         if (full) {
           *reinterpret_cast<f32x4*>(dst) = v;
         } else if (row < g.M) {
@@ -768,7 +742,6 @@ __global__ __launch_bounds__(256, 2) void sim_fp8_kernel(const GemmArgs g) {
           for (int e = 0; e < 4; ++e)
             if (col + e < g.N) dst[e] = v[e];
         }
-#endif
       }
     } else {
 #pragma unroll

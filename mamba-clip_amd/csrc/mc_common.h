@@ -289,6 +289,14 @@ const char* last_error();
     }                                  \
   } while (0)
 
+// Bijective blockIdx remap so that consecutive logical blocks (neighbours that
+// share operands) run on one XCD: hardware deals blocks round-robin over
+// the 8 XCDs (speed only -- correctness never depends on placement).
+__device__ __forceinline__ int xcd_remap(int bid, int nblocks) {
+  const int xcd = bid & 7, q = nblocks >> 3, r = nblocks & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+}
+
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace mc

@@ -25,13 +25,11 @@
 // workgroup would emit a full fp32 partial of both weights.
 #include <type_traits>
 
-#include "scan_common.h"
+#include "mc_common.h"
 #include "../../include/mc_ops.h"
 
 namespace mc {
 namespace mproj {
-using scan::Mfma16;
-using scan::xcd_remap;
 
 constexpr int kTT = 64;                 // tokens per workgroup
 constexpr int kKC = 64;                 // channels per staged chunk
@@ -40,6 +38,17 @@ constexpr int kPMax = 128;              // x_dbl rows supported (R + 2N)
 constexpr int kWaves = 8;              // two waves per SIMD per workgroup: the K loops are latency-bound
 constexpr int kThreads = 64 * kWaves;
 template <int I> using IC = std::integral_constant<int, I>;
+
+// MFMA operand vectors of a 16x16x16 tile (4 16-bit values per lane)
+template <typename TI> struct Mfma16;
+template <> struct Mfma16<bf16_t> {
+  typedef short v4 __attribute__((ext_vector_type(4)));
+  static __device__ __forceinline__ f32x4 mma(v4 a, v4 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, c, 0, 0, 0); }
+};
+template <> struct Mfma16<f16_t> {
+  typedef _Float16 v4 __attribute__((ext_vector_type(4)));
+  static __device__ __forceinline__ f32x4 mma(v4 a, v4 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0); }
+};
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;

@@ -136,10 +136,12 @@ struct ChunkRows {
   __device__ static __forceinline__ int off(int r, int c) { return r * RB + ((c ^ ((r >> kShift) & (VPR - 1))) << 4); }
 };
 
+// 2 waves per SIMD where registers and LDS allow it (16-bit rows, kN <= 16): <= 256 VGPRs,
+// <= 40 KB LDS per workgroup; fp32 rows or kN = 32 run at one wave per SIMD.
 // kDirs: grouped-direction addressing (reverse_groups / u_groups) compiled in; the plain
 // instantiation carries none of it.
-template <typename TI, int kN, bool kAligned, bool kSP, int kMinW, bool kDirs = false>
-__global__ __launch_bounds__(kWG, kMinW) void scan_bwd_kernel(const BwdArgs a) {
+template <typename TI, int kN, bool kAligned, bool kSP, bool kDirs = false>
+__global__ __launch_bounds__(kWG, (sizeof(TI) == 2 && kN <= 16) ? 2 : 1) void scan_bwd_kernel(const BwdArgs a) {
   using CR = ChunkRows<TI>;
   constexpr int VI = ElemTraits<TI>::kVec;   // elements per 16-B vector
   constexpr int VPR = CR::VPR;
@@ -751,27 +753,24 @@ static size_t bwd_lds_bytes() {
 template <typename TI, int kN>
 static int launch_bwd_n(const BwdArgs& a, bool aligned, hipStream_t s) {
   const size_t lds = bwd_lds_bytes<TI, kN>();
-  // 2 waves per SIMD where registers and LDS allow it (16-bit rows, kN <= 16): <= 256 VGPRs,
-  // <= 40 KB LDS per workgroup; fp32 rows or kN = 32 run at one wave per SIMD.
-  constexpr int kMinW = (sizeof(TI) == 2 && kN <= 16) ? 2 : 1;
   if (a.rev_groups || a.u_groups) {   // grouped directions (SS2D)
     if (aligned && a.softplus)
-      hipLaunchKernelGGL((scan_bwd_kernel<TI, kN, true, true, kMinW, true>), dim3(a.total_blocks), dim3(kWG), lds, s, a);
+      hipLaunchKernelGGL((scan_bwd_kernel<TI, kN, true, true, true>), dim3(a.total_blocks), dim3(kWG), lds, s, a);
     else if (aligned)
-      hipLaunchKernelGGL((scan_bwd_kernel<TI, kN, true, false, kMinW, true>), dim3(a.total_blocks), dim3(kWG), lds, s, a);
+      hipLaunchKernelGGL((scan_bwd_kernel<TI, kN, true, false, true>), dim3(a.total_blocks), dim3(kWG), lds, s, a);
     else if (a.softplus)
-      hipLaunchKernelGGL((scan_bwd_kernel<TI, kN, false, true, kMinW, true>), dim3(a.total_blocks), dim3(kWG), lds, s, a);
+      hipLaunchKernelGGL((scan_bwd_kernel<TI, kN, false, true, true>), dim3(a.total_blocks), dim3(kWG), lds, s, a);
     else
-      hipLaunchKernelGGL((scan_bwd_kernel<TI, kN, false, false, kMinW, true>), dim3(a.total_blocks), dim3(kWG), lds, s,
+      hipLaunchKernelGGL((scan_bwd_kernel<TI, kN, false, false, true>), dim3(a.total_blocks), dim3(kWG), lds, s,
                          a);
   } else if (aligned && a.softplus)
-    hipLaunchKernelGGL((scan_bwd_kernel<TI, kN, true, true, kMinW>), dim3(a.total_blocks), dim3(kWG), lds, s, a);
+    hipLaunchKernelGGL((scan_bwd_kernel<TI, kN, true, true>), dim3(a.total_blocks), dim3(kWG), lds, s, a);
   else if (aligned)
-    hipLaunchKernelGGL((scan_bwd_kernel<TI, kN, true, false, kMinW>), dim3(a.total_blocks), dim3(kWG), lds, s, a);
+    hipLaunchKernelGGL((scan_bwd_kernel<TI, kN, true, false>), dim3(a.total_blocks), dim3(kWG), lds, s, a);
   else if (a.softplus)
-    hipLaunchKernelGGL((scan_bwd_kernel<TI, kN, false, true, kMinW>), dim3(a.total_blocks), dim3(kWG), lds, s, a);
+    hipLaunchKernelGGL((scan_bwd_kernel<TI, kN, false, true>), dim3(a.total_blocks), dim3(kWG), lds, s, a);
   else
-    hipLaunchKernelGGL((scan_bwd_kernel<TI, kN, false, false, kMinW>), dim3(a.total_blocks), dim3(kWG), lds, s, a);
+    hipLaunchKernelGGL((scan_bwd_kernel<TI, kN, false, false>), dim3(a.total_blocks), dim3(kWG), lds, s, a);
   const hipError_t e = hipGetLastError();
   MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "mc_scan_bwd: launch failed: %s", hipGetErrorString(e));
   return MC_OK;

@@ -67,26 +67,17 @@ constexpr int kQpEven = 0xA0;   // [0,0,2,2]: the even lane of each pair
 constexpr int kQpOdd = 0xF5;    // [1,1,3,3]: the odd lane
 constexpr int kQpXor1 = 0xB1;   // [1,0,3,2]
 constexpr int kQpXor2 = 0x4E;   // [2,3,0,1]
-__device__ __forceinline__ float row_xor8(float v) {   // row_ror:8 == lane ^ 8 inside a 16-lane row
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float row_xor4(float v) {   // banks 0 / 2 take lane + 4, banks 1 / 3 lane - 4
-  const int iv = __float_as_int(v);
-  const int lo = __builtin_amdgcn_update_dpp(iv, iv, 0x104, 0xF, 0x5, false);
-  return __int_as_float(__builtin_amdgcn_update_dpp(lo, iv, 0x114, 0xF, 0xA, false));
-}
 
 // Halving stages inside a 16-lane row with bank-masked DPP adds (inline asm: hipcc cannot express
 // a write-masked DPP op).  halve_bit3: lanes with bit 3 clear return a + a[lane ^ 8], the others
 // b + b[lane ^ 8]; halve_bit2: bit 2 clear -> a + a[lane + 4], set -> b + b[lane - 4].  The leading
 // s_nop 1 covers the VALU-write -> DPP-read hazard (hipcc pads nothing inside asm).  Same sums,
 // same order as the select form (own + partner).
-#ifndef MC_BWD_SELECT_HALVES
 __device__ __forceinline__ float halve_bit3(float a, float b) {
   float r;
   asm volatile("s_nop 1\n\t"
                "v_add_f32_dpp %0, %1, %1 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
-               "v_add_f32_dpp %0, %2, %2 row_ror:8 row_mask:0xf bank_mask:0xc" MC_ASM_TAIL
+               "v_add_f32_dpp %0, %2, %2 row_ror:8 row_mask:0xf bank_mask:0xc"
                : "=&v"(r) : "v"(a), "v"(b));
   return r;
 }
@@ -94,47 +85,26 @@ __device__ __forceinline__ float halve_bit2(float a, float b) {
   float r;
   asm volatile("s_nop 1\n\t"
                "v_add_f32_dpp %0, %1, %1 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
-               "v_add_f32_dpp %0, %2, %2 row_shr:4 row_mask:0xf bank_mask:0xa" MC_ASM_TAIL
+               "v_add_f32_dpp %0, %2, %2 row_shr:4 row_mask:0xf bank_mask:0xa"
                : "=&v"(r) : "v"(a), "v"(b));
   return r;
 }
-#else
-// A/B (hazard audit): the same halvings as keep / send selects around compiler DPP moves
-__device__ __forceinline__ float halve_bit3(float a, float b) {
-  const bool hi = (__lane_id() >> 3) & 1;
-  const float keep = hi ? b : a, send = hi ? a : b;
-  return keep + row_xor8(send);
-}
-__device__ __forceinline__ float halve_bit2(float a, float b) {
-  const bool hi = (__lane_id() >> 2) & 1;
-  const float keep = hi ? b : a, send = hi ? a : b;
-  return keep + row_xor4(send);
-}
-#endif
 
 // Finishing of one position's state sums: lanes of half h keep pair (h ? b : a) and add the partner
 // lane's (lane ^ 1) other pair, each pair summed over its two states first.  The two pair sums and
 // the DPP add are asm so that the compiler neither SLP-packs the sums (it did, into more
 // instructions) nor keeps the DPP move apart from the add: 2 adds, 2 selects, 1 DPP add instead
 // of 4 selects, 2 adds, a DPP move and an add.  Same sums, same order as before.
-#ifndef MC_BWD_C_FINISH
 __device__ __forceinline__ float pair_finish(f32x2 a, f32x2 b, int h) {
   float sa, sb, r;
-  asm(MC_ASM_HEAD "v_add_f32_e32 %0, %1, %2" MC_ASM_TAIL : "=v"(sa) : "v"(a.x), "v"(a.y));
-  asm(MC_ASM_HEAD "v_add_f32_e32 %0, %1, %2" MC_ASM_TAIL : "=v"(sb) : "v"(b.x), "v"(b.y));
+  asm("v_add_f32_e32 %0, %1, %2" : "=v"(sa) : "v"(a.x), "v"(a.y));
+  asm("v_add_f32_e32 %0, %1, %2" : "=v"(sb) : "v"(b.x), "v"(b.y));
   const float keep = h ? sb : sa, send = h ? sa : sb;
   asm("s_nop 1\n\t"
-      "v_add_f32_dpp %0, %1, %2 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1" MC_ASM_TAIL
+      "v_add_f32_dpp %0, %1, %2 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1"
       : "=v"(r) : "v"(send), "v"(keep));
   return r;
 }
-#else
-__device__ __forceinline__ float pair_finish(f32x2 a, f32x2 b, int h) {   // A/B (hazard audit): compiler code
-  const float sa = a.x + a.y, sb = b.x + b.y;
-  const float keep = h ? sb : sa, send = h ? sa : sb;
-  return keep + qperm<kQpXor1>(send);
-}
-#endif
 
 // Sum of 16 per-lane values (8 packed pairs, value k = 2t + s in v[t].{x|y}) over the 32 lanes of
 // the same lane bit 0 (the wave's 32 channels).  Lane l ends with value k = l >> 2 (lanes l and l ^ 2
@@ -148,42 +118,18 @@ __device__ __forceinline__ float pair_reduce16(f32x2 (&v)[8], int lane) {
   // >= 2 wait states between the last product and the first swap (tools/hazard_scan.py).
   asm volatile("s_nop 1" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]),
                "+v"(v[7]));
-#ifdef MC_BWD_BPERMUTE   // diagnostic: the two cross-row halvings through ds_bpermute, no permlane swaps
-  {
-    const bool up32 = lane & 32, up16 = lane & 16;
-    const int p32 = (lane ^ 32) << 2, p16 = (lane ^ 16) << 2;
-    auto xch = [](int addr, float v) { return __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(v))); };
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const f32x2 keep = up32 ? v[t + 4] : v[t], send = up32 ? v[t] : v[t + 4];
-      v[t] = keep + f32x2{xch(p32, send.x), xch(p32, send.y)};
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const f32x2 keep = up16 ? v[t + 2] : v[t], send = up16 ? v[t] : v[t + 2];
-      v[t] = keep + f32x2{xch(p16, send.x), xch(p16, send.y)};
-    }
-  }
-#else
 #pragma unroll
   for (int t = 0; t < 4; ++t) {   // bit 5: t <-> t + 4
     auto rx = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[t].x), __float_as_uint(v[t + 4].x), false, false);
     auto ry = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[t].y), __float_as_uint(v[t + 4].y), false, false);
-#ifdef MC_PERMLANE_NOP
-    asm volatile("s_nop 4" : "+v"(rx[0]), "+v"(rx[1]), "+v"(ry[0]), "+v"(ry[1]));
-#endif
     v[t] = f32x2{__uint_as_float(rx[0]), __uint_as_float(ry[0])} + f32x2{__uint_as_float(rx[1]), __uint_as_float(ry[1])};
   }
 #pragma unroll
   for (int t = 0; t < 2; ++t) {   // bit 4: t <-> t + 2
     auto rx = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[t].x), __float_as_uint(v[t + 2].x), false, false);
     auto ry = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[t].y), __float_as_uint(v[t + 2].y), false, false);
-#ifdef MC_PERMLANE_NOP
-    asm volatile("s_nop 4" : "+v"(rx[0]), "+v"(rx[1]), "+v"(ry[0]), "+v"(ry[1]));
-#endif
     v[t] = f32x2{__uint_as_float(rx[0]), __uint_as_float(ry[0])} + f32x2{__uint_as_float(rx[1]), __uint_as_float(ry[1])};
   }
-#endif
   // bit 3: t = 0 <-> 1 and bit 2: s = 0 <-> 1 as bank-masked DPP adds (each half of a 16-lane row
   // writes its own sum), instead of keep / send selects around a DPP move
   const float x = halve_bit3(v[0].x, v[1].x), y = halve_bit3(v[0].y, v[1].y);
@@ -213,13 +159,6 @@ __device__ __forceinline__ f32x2 elem2(uint2 w, int i) {   // elements 2i, 2i + 
   const uint4 q = make_uint4(w.x, w.y, 0u, 0u);
   return f32x2{elem_f<TI>(q, 2 * i), elem_f<TI>(q, 2 * i + 1)};
 }
-
-#ifdef MC_BWD_DEBUG
-// Diagnostic build only: per (workgroup, wave, chunk, sub-tile, lane) snapshots of the reverse
-// sweep's carries, written to a library-owned buffer that the host copies out (mc_debug_copy).
-__device__ float* g_dbg = nullptr;
-constexpr int kDbgVals = 32;   // floats per lane and sub-tile: hcar[4] (8), dA2[4] (8), A2[4] (8), entry state (8)
-#endif
 
 template <typename TI, bool kSP, bool kZ, bool kFine>
 __global__ __launch_bounds__(64 * kQW, 2) void scan_bwd_pair_kernel(const BwdPairArgs a) {
@@ -435,10 +374,10 @@ __global__ __launch_bounds__(64 * kQW, 2) void scan_bwd_pair_kernel(const BwdPai
         for (int t = 0; t < kQT; ++t) {
 #pragma unroll
           for (int p = 0; p < kQP; ++p) {
-            const f32x2 arg = (t & 1) ? pk_mul_bcast_safe<1>(A2[p], sc.dt[t >> 1]) : pk_mul_bcast_safe<0>(A2[p], sc.dt[t >> 1]);
+            const f32x2 arg = (t & 1) ? pk_mul_bcast<1>(A2[p], sc.dt[t >> 1]) : pk_mul_bcast<0>(A2[p], sc.dt[t >> 1]);
             const f32x2 aa = f32x2{fast_exp2(arg.x), fast_exp2(arg.y)};
             const f32x2 bb = bpair(kQT * s + t, p);
-            const f32x2 bu = (t & 1) ? pk_mul_bcast_safe<1>(bb, sc.dtu[t >> 1]) : pk_mul_bcast_safe<0>(bb, sc.dtu[t >> 1]);
+            const f32x2 bu = (t & 1) ? pk_mul_bcast<1>(bb, sc.dtu[t >> 1]) : pk_mul_bcast<0>(bb, sc.dtu[t >> 1]);
             x[p] = aa * x[p] + bu;
           }
         }
@@ -451,9 +390,6 @@ __global__ __launch_bounds__(64 * kQW, 2) void scan_bwd_pair_kernel(const BwdPai
     // ---- sub-tiles in reverse
 #pragma unroll 1
     for (int s = nsub - 1; s >= 0; --s) {
-#ifdef MC_BWD_VM0
-      __builtin_amdgcn_s_waitcnt(0x0F70);   // diagnostic: every VMEM op retired before the rows are read
-#endif
       const uint2 ru = nu, rd = nd, rz = nz, rg = ng;
       // next step; after s = 0 the next chunk's first step (full chunk: its last sub-tile when fine)
       load_raw(s > 0 ? l0 + kQT * (s - 1) : (fine ? l0 - kQT : l0 - kS));
@@ -486,16 +422,16 @@ __global__ __launch_bounds__(64 * kQW, 2) void scan_bwd_pair_kernel(const BwdPai
         f32x2 as[kQT], xs[kQT];
 #pragma unroll
         for (int t = 0; t < kQT; ++t) {
-          const f32x2 arg = (t & 1) ? pk_mul_bcast_safe<1>(a2p, sc.dt[t >> 1]) : pk_mul_bcast_safe<0>(a2p, sc.dt[t >> 1]);
-          as[t] = f32x2{pexp2(arg.x), pexp2(arg.y)};
+          const f32x2 arg = (t & 1) ? pk_mul_bcast<1>(a2p, sc.dt[t >> 1]) : pk_mul_bcast<0>(a2p, sc.dt[t >> 1]);
+          as[t] = f32x2{fast_exp2(arg.x), fast_exp2(arg.y)};
         }
         {   // (B dt u off the chain: one pk_fma per step on it)
           f32x2 x = xin;
 #pragma unroll
           for (int t = 0; t < kQT; ++t) {
             const f32x2 bb = bpair(kQT * s + t, p);
-            const f32x2 bu = (t & 1) ? pk_mul_bcast_safe<1>(bb, sc.dtu[t >> 1]) : pk_mul_bcast_safe<0>(bb, sc.dtu[t >> 1]);
-            x = pfma(as[t], x, bu);
+            const f32x2 bu = (t & 1) ? pk_mul_bcast<1>(bb, sc.dtu[t >> 1]) : pk_mul_bcast<0>(bb, sc.dtu[t >> 1]);
+            x = as[t] * x + bu;
             xs[t] = x;
           }
         }
@@ -504,7 +440,7 @@ __global__ __launch_bounds__(64 * kQW, 2) void scan_bwd_pair_kernel(const BwdPai
           f32x2 red[kQT];
 #pragma unroll
           for (int t = 0; t < kQT; ++t)
-            red[t] = (t & 1) ? pk_mul_bcast_safe<1>(xs[t], sc.gy[t >> 1]) : pk_mul_bcast_safe<0>(xs[t], sc.gy[t >> 1]);
+            red[t] = (t & 1) ? pk_mul_bcast<1>(xs[t], sc.gy[t >> 1]) : pk_mul_bcast<0>(xs[t], sc.gy[t >> 1]);
           const float v = pair_reduce16(red, lane);
           if ((lane & 2) == 0)
             dbc[((kQT * s + (lane >> 3)) * 2 + 1) * kQN + 8 * h + 2 * p + ((lane >> 2) & 1)] = v;
@@ -519,15 +455,15 @@ __global__ __launch_bounds__(64 * kQW, 2) void scan_bwd_pair_kernel(const BwdPai
           for (int t = kQT - 1; t >= 0; --t) {
             const f32x4 q = qn;
             if (t > 0) qn = bquad(kQT * s + t - 1, p);
-            lam = (t & 1) ? pk_fma_bcast_safe<1>(q.hi, sc.gy[t >> 1], t == kQT - 1 ? hcar[p] : ha)
-                          : pk_fma_bcast_safe<0>(q.hi, sc.gy[t >> 1], t == kQT - 1 ? hcar[p] : ha);
-            if (hasZ) Y2[t] = pfma(q.hi, xs[t], Y2[t]);
-            S2[t] = pfma(lam, q.lo, S2[t]);
-            red[t] = (t & 1) ? pk_mul_bcast_safe<1>(lam, sc.dtu[t >> 1]) : pk_mul_bcast_safe<0>(lam, sc.dtu[t >> 1]);
-            ha = pmul(lam, as[t]);
-            const f32x2 hax = pmul(ha, t > 0 ? xs[t - 1] : xin);
-            Q2[t] = pfma(hax, a2p, Q2[t]);
-            dap = (t & 1) ? pk_fma_bcast_safe<1>(hax, sc.dt[t >> 1], dap) : pk_fma_bcast_safe<0>(hax, sc.dt[t >> 1], dap);
+            lam = (t & 1) ? pk_fma_bcast<1>(q.hi, sc.gy[t >> 1], t == kQT - 1 ? hcar[p] : ha)
+                          : pk_fma_bcast<0>(q.hi, sc.gy[t >> 1], t == kQT - 1 ? hcar[p] : ha);
+            if (hasZ) Y2[t] = q.hi * xs[t] + Y2[t];
+            S2[t] = lam * q.lo + S2[t];
+            red[t] = (t & 1) ? pk_mul_bcast<1>(lam, sc.dtu[t >> 1]) : pk_mul_bcast<0>(lam, sc.dtu[t >> 1]);
+            ha = lam * as[t];
+            const f32x2 hax = ha * (t > 0 ? xs[t - 1] : xin);
+            Q2[t] = hax * a2p + Q2[t];
+            dap = (t & 1) ? pk_fma_bcast<1>(hax, sc.dt[t >> 1], dap) : pk_fma_bcast<0>(hax, sc.dt[t >> 1], dap);
           }
           asm volatile("" : "+v"(ha), "+v"(dap));
 #pragma unroll
@@ -583,20 +519,6 @@ __global__ __launch_bounds__(64 * kQW, 2) void scan_bwd_pair_kernel(const BwdPai
           dbacc += dd.x + dd.y;
         }
       }
-#ifdef MC_BWD_DEBUG
-      if (g_dbg) {
-        const int nch_ = (L_ + kS - 1) / kS;
-        float* d = g_dbg + ((((int64_t)lin * kQW + wave) * nch_ + c) * kQSub + s) * 64 * kDbgVals + lane * kDbgVals;
-#pragma unroll
-        for (int p = 0; p < kQP; ++p) {
-          d[2 * p] = hcar[p].x; d[2 * p + 1] = hcar[p].y;
-          d[8 + 2 * p] = dA2[p].x; d[8 + 2 * p + 1] = dA2[p].y;
-          d[16 + 2 * p] = A2[p].x; d[16 + 2 * p + 1] = A2[p].y;
-        }
-        d[24] = xi01.x; d[25] = xi01.y; d[26] = xi01.z; d[27] = xi01.w;
-        d[28] = xi23.x; d[29] = xi23.y; d[30] = xi23.z; d[31] = xi23.w;
-      }
-#endif
       const uint32_t e0 = (uint32_t)(l0 + kQT * s + 4 * h);
       buf_st8(rs_du, ((ro_du + e0) * 2u) | st_mask, make_uint2(cvt_pk2<TI>(o_du[0], o_du[1]), cvt_pk2<TI>(o_du[2], o_du[3])));
       buf_st8(rs_dd, ((ro_dd + e0) * 2u) | st_mask, make_uint2(cvt_pk2<TI>(o_dd[0], o_dd[1]), cvt_pk2<TI>(o_dd[2], o_dd[3])));
@@ -713,23 +635,3 @@ void launch_bwd_pair(const mc_scan_bwd_params* p, float* slab_bc, float* slab_a,
 
 }  // namespace scan
 }  // namespace mc
-
-#ifdef MC_BWD_DEBUG
-extern "C" int mc_debug_alloc(size_t bytes) {
-  static float* buf = nullptr;
-  static size_t have = 0;
-  if (bytes > have) {
-    if (buf) (void)hipFree(buf);
-    if (hipMalloc(&buf, bytes) != hipSuccess) return 1;
-    have = bytes;
-  }
-  (void)hipMemset(buf, 0, bytes);
-  float* p = bytes ? buf : nullptr;
-  return hipMemcpyToSymbol(HIP_SYMBOL(mc::scan::g_dbg), &p, sizeof(p)) == hipSuccess ? 0 : 2;
-}
-extern "C" int mc_debug_copy(void* dst, size_t bytes, void* stream) {
-  float* p = nullptr;
-  if (hipMemcpyFromSymbol(&p, HIP_SYMBOL(mc::scan::g_dbg), sizeof(p)) != hipSuccess || !p) return 1;
-  return hipMemcpyAsync(dst, p, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) == hipSuccess ? 0 : 2;
-}
-#endif

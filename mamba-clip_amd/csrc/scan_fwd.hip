@@ -27,7 +27,6 @@
 
 #include "scan_common.h"
 
-
 namespace mc {
 namespace scan {
 
@@ -35,14 +34,145 @@ namespace scan {
 bool fwd_pair_ok(const FwdArgs& a, bool aligned, int itype_bytes, int itype, int wtype);   // scan_fwd_pair.hip
 int launch_fwd_pair(const FwdArgs& a, int itype, hipStream_t s);
 
+// B/C as the recurrence consumes them: fp32, position-major, [b][g][l][2*kNp]
+// (B states 0..kNp-1 then C states; states >= dstate are zero).  Every lane of
+// a wave reads the same position, so one chunk of it is a contiguous block
+// that is staged in LDS once per wave and broadcast-read.
+static size_t bct_bytes(int batch, int seqlen, int dstate, int n_groups) {
+  return (size_t)batch * n_groups * seqlen * 2 * padded_dstate(dstate) * sizeof(float);
+}
 
-// Variants (template knobs, chosen on the host):
-//   kG     steps per group of the recurrence loop: the B/C values of a group
-//          are read from LDS together (kG * 2 * kN VGPRs live)
-//   kPBC   prefetch the next chunk's B/C into registers (else: load at staging)
-//   kPU    prefetch the next chunk's u / delta into registers (else: load at staging)
-//   kMinW  waves per SIMD the register budget is sized for
-// At C4 (B=64, D=3072: 3072 one-wave workgroups on 1024 SIMDs) the kernel is
+// Re-lay B/C (any strides along b/g/n, unit stride along l) into the fp32
+// position-major buffer.  One thread per (b, g, l, j<2kNp).
+template <typename TW, int kNp>
+__global__ __launch_bounds__(256) void bc_relayout_kernel(const TW* __restrict__ B, const TW* __restrict__ C,
+                                                         int64_t B_bs, int64_t B_gs, int64_t B_ns, int64_t C_bs,
+                                                         int64_t C_gs, int64_t C_ns, int batch, int G, int L,
+                                                         int dstate, int rev, float* __restrict__ out) {
+  const int64_t total = (int64_t)batch * G * L * 2 * kNp;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int j = (int)(i % (2 * kNp));
+    const int64_t rest = i / (2 * kNp);
+    const int l = (int)(rest % L);
+    const int64_t bg = rest / L;
+    const int g = (int)(bg % G), b = (int)(bg / G);
+    const bool isC = j >= kNp;
+    const int n = isC ? j - kNp : j;
+    float v = 0.f;
+    if (n < dstate) {
+      const TW* src = isC ? C + (int64_t)b * C_bs + (int64_t)g * C_gs + (int64_t)n * C_ns
+                          : B + (int64_t)b * B_bs + (int64_t)g * B_gs + (int64_t)n * B_ns;
+      v = to_f(src[((rev >> g) & 1) ? L - 1 - l : l]);   // reversed groups: mirrored positions
+    }
+    out[i] = v;
+  }
+}
+
+// Vector form for 16-bit B/C with 16-B aligned rows, L % 8 == 0 and no reversed groups (every
+// long-sequence call): one thread per (b, g, 8-position block, B|C half) reads kNp 16-B row
+// vectors and writes its half of 8 position rows as float4s (the element-wise kernel above
+// moves 2-B loads and 4-B stores: 31 us at C4).
+template <typename TW, int kNp>
+__global__ __launch_bounds__(256) void bc_relayout_vec_kernel(const TW* __restrict__ B, const TW* __restrict__ C,
+                                                             int64_t B_bs, int64_t B_gs, int64_t B_ns, int64_t C_bs,
+                                                             int64_t C_gs, int64_t C_ns, int batch, int G, int L,
+                                                             int dstate, float* __restrict__ out) {
+  const int nblk = L / 8;
+  const int64_t total = (int64_t)batch * G * nblk * 2;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int half = (int)(i & 1);
+    const int64_t rest = i >> 1;
+    const int lb = (int)(rest % nblk);
+    const int64_t bg = rest / nblk;
+    const int g = (int)(bg % G), b = (int)(bg / G);
+    const TW* src = half ? C + (int64_t)b * C_bs + (int64_t)g * C_gs : B + (int64_t)b * B_bs + (int64_t)g * B_gs;
+    const int64_t ns = half ? C_ns : B_ns;
+    uint4 q[kNp];
+#pragma unroll
+    for (int n = 0; n < kNp; ++n)
+      q[n] = n < dstate ? ld16(src + (int64_t)n * ns + 8 * lb) : make_uint4(0u, 0u, 0u, 0u);
+    float* dst = out + ((bg * L + 8 * lb) * 2 + half) * kNp;
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+#pragma unroll
+      for (int n4 = 0; n4 < kNp / 4; ++n4)
+        reinterpret_cast<float4*>(dst + e * 2 * kNp)[n4] =
+            make_float4(elem_f<TW>(q[4 * n4], e), elem_f<TW>(q[4 * n4 + 1], e), elem_f<TW>(q[4 * n4 + 2], e),
+                        elem_f<TW>(q[4 * n4 + 3], e));
+  }
+}
+
+template <typename TW>
+static hipError_t launch_bc_relayout(const void* B, const void* C, int64_t B_bs, int64_t B_gs, int64_t B_ns,
+                                     int64_t C_bs, int64_t C_gs, int64_t C_ns, int batch, int G, int L, int dstate,
+                                     int rev, float* out, hipStream_t s) {
+  const int np = padded_dstate(dstate);
+  const TW* b = reinterpret_cast<const TW*>(B);
+  const TW* c = reinterpret_cast<const TW*>(C);
+  if constexpr (sizeof(TW) == 2) {
+    auto al = [](const void* p, int64_t s0, int64_t s1, int64_t s2) {
+      return aligned16(p) && s0 % 8 == 0 && s1 % 8 == 0 && s2 % 8 == 0;
+    };
+    if (rev == 0 && L % 8 == 0 && al(B, B_bs, B_gs, B_ns) && al(C, C_bs, C_gs, C_ns) && np >= 8) {
+      const int64_t tv = (int64_t)batch * G * (L / 8) * 2;
+      const int gv = (int)std::min<int64_t>((tv + 255) / 256, 16384);
+      if (np == 8)
+        hipLaunchKernelGGL((bc_relayout_vec_kernel<TW, 8>), gv, 256, 0, s, b, c, B_bs, B_gs, B_ns, C_bs, C_gs, C_ns,
+                           batch, G, L, dstate, out);
+      else if (np == 16)
+        hipLaunchKernelGGL((bc_relayout_vec_kernel<TW, 16>), gv, 256, 0, s, b, c, B_bs, B_gs, B_ns, C_bs, C_gs, C_ns,
+                           batch, G, L, dstate, out);
+      else
+        hipLaunchKernelGGL((bc_relayout_vec_kernel<TW, 32>), gv, 256, 0, s, b, c, B_bs, B_gs, B_ns, C_bs, C_gs, C_ns,
+                           batch, G, L, dstate, out);
+      return hipGetLastError();
+    }
+  }
+  const int64_t total = (int64_t)batch * G * L * 2 * np;
+  const int grid = (int)std::min<int64_t>((total + 255) / 256, 8192);
+  if (np == 8)
+    hipLaunchKernelGGL((bc_relayout_kernel<TW, 8>), grid, 256, 0, s, b, c, B_bs, B_gs, B_ns, C_bs, C_gs, C_ns, batch,
+                       G, L, dstate, rev, out);
+  else if (np == 16)
+    hipLaunchKernelGGL((bc_relayout_kernel<TW, 16>), grid, 256, 0, s, b, c, B_bs, B_gs, B_ns, C_bs, C_gs, C_ns,
+                       batch, G, L, dstate, rev, out);
+  else
+    hipLaunchKernelGGL((bc_relayout_kernel<TW, 32>), grid, 256, 0, s, b, c, B_bs, B_gs, B_ns, C_bs, C_gs, C_ns,
+                       batch, G, L, dstate, rev, out);
+  return hipGetLastError();
+}
+
+static hipError_t relayout_bc(int wtype, const void* B, const void* C, int64_t B_bs, int64_t B_gs, int64_t B_ns,
+                              int64_t C_bs, int64_t C_gs, int64_t C_ns, int batch, int G, int L, int dstate,
+                              int rev, float* out, hipStream_t s) {
+  if (wtype == MC_DTYPE_F32)
+    return launch_bc_relayout<float>(B, C, B_bs, B_gs, B_ns, C_bs, C_gs, C_ns, batch, G, L, dstate, rev, out, s);
+  if (wtype == MC_DTYPE_BF16)
+    return launch_bc_relayout<bf16_t>(B, C, B_bs, B_gs, B_ns, C_bs, C_gs, C_ns, batch, G, L, dstate, rev, out, s);
+  return launch_bc_relayout<f16_t>(B, C, B_bs, B_gs, B_ns, C_bs, C_gs, C_ns, batch, G, L, dstate, rev, out, s);
+}
+
+// LDS row of one channel for one chunk: kT / VI blocks; block k = {u vector k
+// (16 B = VI steps), delta vector k (16 B)}.  After consuming block k the
+// thread writes y for those VI steps (fp32, 4*VI <= 32 B) over the block, so
+// the y tile costs no extra LDS.  Row stride = data + 16 B: conflict-free
+// ds_read_b128 when every lane reads its own row.
+template <typename TI>
+struct RowLayout {
+  static constexpr int VI = ElemTraits<TI>::kVec;
+  static constexpr int kBlock = 32;
+  static constexpr int kBlocks = kT / VI;
+  static constexpr int kBytes = kBlocks * kBlock;
+  static constexpr int kStride = kBytes + 16;
+};
+
+
+// The long-sequence kernel: the recurrence runs in groups of kG = 4 steps whose u / delta are read
+// from LDS together and whose four fp32 y values go back over exactly those bytes; the next chunk's
+// u / delta vectors and B/C block are prefetched into registers under the current chunk's recurrence.
+// 16-bit rows are sized for 2 waves per SIMD; fp32 rows double the prefetch registers, and one wave
+// per SIMD keeps them out of scratch (the SS2D grids are a few hundred waves, occupancy buys nothing
+// there).  At C4 (B=64, D=3072: 3072 one-wave workgroups on 1024 SIMDs) the kernel is
 // VALU + v_exp issue bound (~33 SIMD cycles per wave per (t, n) step, measured
 // the same at 1 and 2 waves per SIMD), not HBM bound.
 // kAligned: 0 = element-wise rows, 1 = 16-B aligned rows, 2 = aligned and every chunk
@@ -50,8 +180,9 @@ int launch_fwd_pair(const FwdArgs& a, int itype, hipStream_t s);
 // budget of the 3-waves-per-SIMD build free of spills)
 // kSP: softplus on delta (a template flag: a runtime one is a uniform branch per position
 // that splits the recurrence into small basic blocks)
-template <typename TI, int kN, int kAligned, int kG, bool kPBC, bool kPU, int kMinW, bool kSP>
-__global__ __launch_bounds__(kRows, kMinW) void scan_fwd_kernel(const FwdArgs a) {
+constexpr int kG = 4;   // steps per recurrence group
+template <typename TI, int kN, int kAligned, bool kSP>
+__global__ __launch_bounds__(kRows, sizeof(TI) == 4 ? 1 : 2) void scan_fwd_kernel(const FwdArgs a) {
   using RL = RowLayout<TI>;
   constexpr int VI = RL::VI;                    // elements per 16-B vector
   constexpr int kVPR = kT / VI;                 // vectors per row segment per array
@@ -120,7 +251,7 @@ __global__ __launch_bounds__(kRows, kMinW) void scan_fwd_kernel(const FwdArgs a)
   constexpr int kBCVec = kT * 2 * kN / 4;                 // float4s in one B/C chunk
   constexpr int kBCPer = (kBCVec + kRows - 1) / kRows;
   uint4 pu[kVPR], pd[kVPR];
-  float4 pbc[kPBC ? kBCPer : 1];
+  float4 pbc[kBCPer];
   // (whole-chunk mode) this (batch, group)'s B/C rows as a buffer range: chunks past
   // the end read 0, so the prefetch needs no branch (a branch around loads makes the
   // compiler drain the stores issued after them before the loads may be consumed)
@@ -178,14 +309,13 @@ __global__ __launch_bounds__(kRows, kMinW) void scan_fwd_kernel(const FwdArgs a)
         pd[k] = ld16_masked(sd, nv);
       }
     }
-    if constexpr (kPBC) load_bc(l0, pbc);
+    load_bc(l0, pbc);
   };
 
-  if constexpr (kPU) load_regs(0);
+  load_regs(0);
   for (int ch = 0; ch < a.n_chunks; ++ch) {
     const int l0 = ch * kT;
     const bool full = kAligned == 2 || (kAligned == 1 && l0 + kT <= L_);
-    if constexpr (!kPU) load_regs(l0);   // other resident waves cover the latency
 
     // ---- stage u / delta (vector j = lane + k*64 -> row j / kVPR, col j % kVPR) and B/C
 #pragma unroll
@@ -198,12 +328,8 @@ __global__ __launch_bounds__(kRows, kMinW) void scan_fwd_kernel(const FwdArgs a)
     }
     {
       float4 cur[kBCPer];
-      if constexpr (kPBC) {
 #pragma unroll
-        for (int k = 0; k < kBCPer; ++k) cur[k] = pbc[k];
-      } else {
-        load_bc(l0, cur);   // L2-resident (shared by the waves of this batch); latency once per chunk
-      }
+      for (int k = 0; k < kBCPer; ++k) cur[k] = pbc[k];
 #pragma unroll
       for (int k = 0; k < kBCPer; ++k) {
         const int v = lane + k * kRows;
@@ -211,10 +337,8 @@ __global__ __launch_bounds__(kRows, kMinW) void scan_fwd_kernel(const FwdArgs a)
       }
     }
     wave_lds_sync();
-    if constexpr (kPU) {
-      if constexpr (kAligned == 2) load_regs(l0 + kT);   // past the end: out-of-range offsets read 0
-      else if (ch + 1 < a.n_chunks) load_regs(l0 + kT);
-    }
+    if constexpr (kAligned == 2) load_regs(l0 + kT);   // past the end: out-of-range offsets read 0
+    else if (ch + 1 < a.n_chunks) load_regs(l0 + kT);
     // this chunk's z vectors (gate pass mapping), loaded now so that they arrive
     // under the recurrence instead of stalling the gate pass
     uint4 cz[kVPR];
@@ -248,14 +372,10 @@ __global__ __launch_bounds__(kRows, kMinW) void scan_fwd_kernel(const FwdArgs a)
           constexpr int kB = kG * (int)sizeof(TI);   // bytes of one array in this group
           uint4 qa, qb;
           if constexpr (kB == 16) { qa = ld16(pu); qb = ld16(pd); }
-          else if constexpr (kB == 8) {
+          else {
+            static_assert(kB == 8, "a group is 16 B (fp32) or 8 B (16-bit) per array");
             const uint2 a2 = *reinterpret_cast<const uint2*>(pu), b2 = *reinterpret_cast<const uint2*>(pd);
             qa = make_uint4(a2.x, a2.y, 0u, 0u); qb = make_uint4(b2.x, b2.y, 0u, 0u);
-          } else if constexpr (kB == 4) {
-            qa = make_uint4(*reinterpret_cast<const uint32_t*>(pu), 0u, 0u, 0u);
-            qb = make_uint4(*reinterpret_cast<const uint32_t*>(pd), 0u, 0u, 0u);
-          } else {
-            static_assert(kB >= 4, "group must cover >= 4 bytes per array");
           }
 #pragma unroll
           for (int e = 0; e < kG; ++e) { uu[e] = elem_f<TI>(qa, e); dd[e] = elem_f<TI>(qb, e); }
@@ -312,14 +432,9 @@ __global__ __launch_bounds__(kRows, kMinW) void scan_fwd_kernel(const FwdArgs a)
             }
           }
         }
-        if constexpr (kG == 4) {
-          *reinterpret_cast<float2*>(pu) = make_float2(yv[0], yv[1]);
-          *reinterpret_cast<float2*>(pd) = make_float2(yv[2], yv[3]);
-        } else {
-          static_assert(kG == 2, "kG in {2, 4}");
-          *reinterpret_cast<float*>(pu) = yv[0];
-          *reinterpret_cast<float*>(pd) = yv[1];
-        }
+        static_assert(kG == 4, "two y values over each array's bytes");
+        *reinterpret_cast<float2*>(pu) = make_float2(yv[0], yv[1]);
+        *reinterpret_cast<float2*>(pd) = make_float2(yv[2], yv[3]);
       }
     }
     wave_lds_sync();
@@ -390,7 +505,7 @@ __global__ __launch_bounds__(kRows, kMinW) void scan_fwd_kernel(const FwdArgs a)
 
 typedef __attribute__((address_space(4))) const f32x4 cf32x4;   // constant address space: scalar loads
 
-// Row layout of the 16-position chunk variants: per row {u vector, delta vector} blocks + 16-B pad.
+// Row layout of the 16-position chunk kernel: per row {u vector, delta vector} blocks + 16-B pad.
 template <typename TI>
 struct RowLayoutP {
   static constexpr int kTP = 16;
@@ -400,17 +515,18 @@ struct RowLayoutP {
   static constexpr int kStride = kBlocks * kBlock + 16;
 };
 
-// ------------------------------------------------------------------ multi-channel-per-lane variant
-// kR channels per lane (a wave owns 64*kR channels of one (batch, group)):
-// the kR recurrences are independent, so they interleave in one instruction
-// stream and hide each other's latencies (ILP instead of resident waves), and
-// each position's B/C row -- loaded once per wave into SGPRs -- serves kR
-// times the work.  At C4 (B=64, D=3072) kR = 3 gives 1024 waves: exactly one
-// per SIMD, no tail round.  u / delta / z of the next chunk are prefetched
-// into registers during the current chunk (z too: the gate pass never waits
-// on HBM).
-template <typename TI, int kN, int kR, bool kAligned, bool kSP>
-__global__ __launch_bounds__(kRows, kR == 1 ? 3 : 1) void scan_fwd_mc_kernel(const FwdArgs a) {
+// ------------------------------------------------------------------ short-sequence kernel
+// One channel per lane like scan_fwd_kernel, but each position's B/C row is loaded once per wave
+// into SGPRs (no LDS staging of B/C), chunks are 16 positions, and the budget is 3 waves per SIMD:
+// with short sequences the grid is many short-lived waves and occupancy hides the latencies.
+// u / delta / z of the next chunk are prefetched into registers during the current chunk (z too:
+// the gate pass never waits on HBM).
+template <typename TI, int kN, bool kAligned, bool kSP>
+__global__ __launch_bounds__(kRows, 3) void scan_fwd_mc_kernel(const FwdArgs a) {
+  // Channels per lane (row lane + 64 r of the wave's block).  Only 1 is built: 3 measured slower (table
+  // above launch_fwd_n).  The loops over r stay: writing them out changes the code the compiler
+  // generates for every instance (profiles/scan_cleanup/isa_identity.txt).
+  constexpr int kR = 1;
   using RL = RowLayoutP<TI>;
   constexpr int kTP = RL::kTP;
   constexpr int VI = RL::VI;
@@ -629,84 +745,63 @@ __global__ __launch_bounds__(kRows, kR == 1 ? 3 : 1) void scan_fwd_mc_kernel(con
   }
 }
 
-template <typename TI, int kN, int kR>
-static int launch_fwd_mc(const FwdArgs& a0, bool aligned, hipStream_t s) {
-  FwdArgs a = a0;
-  const int H = a.dim / a.n_groups;
-  a.nblk = (H + kRows * kR - 1) / (kRows * kR);
-  a.total_blocks = a.batch * a.n_groups * a.nblk;
-  const size_t lds = (size_t)kRows * kR * RowLayoutP<TI>::kStride;
-  if (aligned && a.softplus)
-    hipLaunchKernelGGL((scan_fwd_mc_kernel<TI, kN, kR, true, true>), dim3(a.total_blocks), dim3(kRows), lds, s, a);
-  else if (aligned)
-    hipLaunchKernelGGL((scan_fwd_mc_kernel<TI, kN, kR, true, false>), dim3(a.total_blocks), dim3(kRows), lds, s, a);
-  else if (a.softplus)
-    hipLaunchKernelGGL((scan_fwd_mc_kernel<TI, kN, kR, false, true>), dim3(a.total_blocks), dim3(kRows), lds, s, a);
-  else
-    hipLaunchKernelGGL((scan_fwd_mc_kernel<TI, kN, kR, false, false>), dim3(a.total_blocks), dim3(kRows), lds, s, a);
-  const hipError_t e = hipGetLastError();
-  MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "mc_scan_fwd: launch failed: %s", hipGetErrorString(e));
-  return MC_OK;
+// ------------------------------------------------------------------ host dispatch
+template <typename TI, int kN>
+static void launch_fwd_mc(const FwdArgs& a, bool aligned, hipStream_t s) {
+  const size_t lds = (size_t)kRows * RowLayoutP<TI>::kStride;
+  const dim3 grid(a.total_blocks), block(kRows);
+  if (aligned && a.softplus) hipLaunchKernelGGL((scan_fwd_mc_kernel<TI, kN, true, true>), grid, block, lds, s, a);
+  else if (aligned) hipLaunchKernelGGL((scan_fwd_mc_kernel<TI, kN, true, false>), grid, block, lds, s, a);
+  else if (a.softplus) hipLaunchKernelGGL((scan_fwd_mc_kernel<TI, kN, false, true>), grid, block, lds, s, a);
+  else hipLaunchKernelGGL((scan_fwd_mc_kernel<TI, kN, false, false>), grid, block, lds, s, a);
 }
 
-// ------------------------------------------------------------------ host dispatch
-template <typename TI, int kN, int kG, bool kPBC, bool kPU, int kMinW>
-static int launch_fwd_v(const FwdArgs& a, bool aligned, hipStream_t s) {
+template <typename TI, int kN>
+static void launch_fwd_lds(const FwdArgs& a, bool aligned, hipStream_t s) {
   const size_t lds = (size_t)kRows * RowLayout<TI>::kStride + (size_t)kT * 2 * kN * 4;
+  const dim3 grid(a.total_blocks), block(kRows);
   auto fits = [&](int64_t ds) {
     return ((int64_t)(kRows - 1) * (ds < 0 ? -ds : ds) + a.seqlen) * (int64_t)sizeof(TI) < ((int64_t)1 << 31);
   };
   const bool span32 = fits(a.o_ds) && fits(a.u_ds) && fits(a.dt_ds) && (!a.z || fits(a.z_ds)) &&
                       (!a.out_y || fits(a.y_ds));
-#define MC_FWD_LAUNCH(AL, SP) \
-  hipLaunchKernelGGL((scan_fwd_kernel<TI, kN, AL, kG, kPBC, kPU, kMinW, SP>), dim3(a.total_blocks), dim3(kRows), lds, s, a)
+#define MC_FWD_LAUNCH(AL, SP) hipLaunchKernelGGL((scan_fwd_kernel<TI, kN, AL, SP>), grid, block, lds, s, a)
   const bool sp = a.softplus != 0;
   if (aligned && a.seqlen % kT == 0 && span32) { if (sp) MC_FWD_LAUNCH(2, true); else MC_FWD_LAUNCH(2, false); }
   else if (aligned) { if (sp) MC_FWD_LAUNCH(1, true); else MC_FWD_LAUNCH(1, false); }
   else { if (sp) MC_FWD_LAUNCH(0, true); else MC_FWD_LAUNCH(0, false); }
 #undef MC_FWD_LAUNCH
-  const hipError_t e = hipGetLastError();
-  MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "mc_scan_fwd: launch failed: %s", hipGetErrorString(e));
-  return MC_OK;
 }
 
-// Kernel choice, measured on MI355X (tools/ab_scan_fwd.sh; ms, bf16, z, softplus):
+// Kernel choice, measured on MI355X (ms, bf16, z, softplus):
 //                                         C4 64x3072x4096   C2 256x1536x80
 //   scan_fwd_kernel (kG 4, LDS B/C, 2 w/SIMD)     3.17 (r01: 3.35) 0.204
-//   scan_fwd_mc_kernel R=1 (SGPR B/C, 16-pos)     3.87             0.152
-//   scan_fwd_mc_kernel R=3 (1 w/SIMD)             3.66             0.180
-// Rejected (kept in git history): per-position LDS broadcast at 3 w/SIMD
+//   scan_fwd_mc_kernel (SGPR B/C, 16-pos)         3.87             0.152
+//   the same with 3 channels per lane (1 w/SIMD)  3.66             0.180
+// Tried, slower (git history has the kernels): per-position LDS broadcast at 3 w/SIMD
 // 3.96 / 0.188; two-wave state split with SGPR half-rows 6.41 / 0.266; two-wave
 // state split with LDS-staged rows and LDS partial-y sums (no 2+1 tail: 6
 // half-tasks per SIMD) 3.92 at C4 -- the per-position work both waves repeat
 // (row reads, softplus, y hand-off) costs more than the tail it removes;
 // vector-load B/C rings spill at the occupancy they need.  With short
 // sequences the grid is many short-lived waves and the SGPR-fed kernel wins;
-// with long ones the LDS-staged kernel's deeper prefetch wins.
-// A/B variants of this choice are built under tools/ (git history has the rejected kernels).
+// with long ones the LDS-staged kernel's deeper prefetch wins.  Grouped directions
+// (per-group addressing) live in the LDS-staged kernel only.
 template <typename TI, int kN>
-static int launch_fwd_n(const FwdArgs& a, bool aligned, hipStream_t s) {
-  if (a.seqlen <= 512) return launch_fwd_mc<TI, kN, 1>(a, aligned, s);
-  return launch_fwd_v<TI, kN, 4, true, true, sizeof(TI) == 4 ? 1 : 2>(a, aligned, s);   // fp32: see launch_fwd_dirs
+static void launch_fwd_n(const FwdArgs& a, bool aligned, bool dirs, hipStream_t s) {
+  if (a.seqlen <= 512 && !dirs) launch_fwd_mc<TI, kN>(a, aligned, s);
+  else launch_fwd_lds<TI, kN>(a, aligned, s);
 }
 
 template <typename TI>
-static int launch_fwd_dirs(const FwdArgs& a, bool aligned, hipStream_t s) {
-  // fp32 rows double the prefetch registers: one wave per SIMD keeps them out of scratch
-  // (the SS2D grids are a few hundred waves, occupancy buys nothing there)
-  constexpr int kW = sizeof(TI) == 4 ? 1 : 2;
+static int launch_fwd_t(const FwdArgs& a, bool aligned, bool dirs, hipStream_t s) {
   const int np = padded_dstate(a.dstate);
-  if (np == 8) return launch_fwd_v<TI, 8, 4, true, true, kW>(a, aligned, s);
-  if (np == 16) return launch_fwd_v<TI, 16, 4, true, true, kW>(a, aligned, s);
-  return launch_fwd_v<TI, 32, 4, true, true, kW>(a, aligned, s);
-}
-
-template <typename TI>
-static int launch_fwd_t(const FwdArgs& a, bool aligned, hipStream_t s) {
-  const int np = padded_dstate(a.dstate);
-  if (np == 8) return launch_fwd_n<TI, 8>(a, aligned, s);
-  if (np == 16) return launch_fwd_n<TI, 16>(a, aligned, s);
-  return launch_fwd_n<TI, 32>(a, aligned, s);
+  if (np == 8) launch_fwd_n<TI, 8>(a, aligned, dirs, s);
+  else if (np == 16) launch_fwd_n<TI, 16>(a, aligned, dirs, s);
+  else launch_fwd_n<TI, 32>(a, aligned, dirs, s);
+  const hipError_t e = hipGetLastError();
+  MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "mc_scan_fwd: launch failed: %s", hipGetErrorString(e));
+  return MC_OK;
 }
 
 int validate_common(int batch, int dim, int seqlen, int dstate, int n_groups, int itype, int wtype, const char* who) {
@@ -779,7 +874,6 @@ extern "C" int mc_scan_fwd(const mc_scan_fwd_params* p, void* stream) {
   bool aligned = false;
   const bool pair = fill_fwd_args(p, a, aligned);
   const int ib = p->itype == MC_DTYPE_F32 ? 4 : 2;
-  (void)dirs;
   MC_CHECK(p->state_interval == 0 || p->state_interval == kS || (p->state_interval == kFineS && pair), MC_ERR_SHAPE,
            "mc_scan_fwd: state_interval %d: 0 / %d, or %d on the pair kernel's shapes (mc_scan_fwd_state_interval)",
            p->state_interval, kS, kFineS);
@@ -791,15 +885,11 @@ extern "C" int mc_scan_fwd(const mc_scan_fwd_params* p, void* stream) {
                              p->seqlen, p->dstate, dirs ? p->reverse_groups : 0,
                              reinterpret_cast<float*>(p->workspace), s);
   MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "mc_scan_fwd: B/C relayout launch failed: %s", hipGetErrorString(e));
-  if (dirs) {   // per-group addressing lives in the LDS-staged kernel (vector modes: seqlen % VI == 0)
-    const bool al = aligned && p->seqlen % (16 / ib) == 0;
-    if (p->itype == MC_DTYPE_F32) return launch_fwd_dirs<float>(a, al, s);
-    if (p->itype == MC_DTYPE_BF16) return launch_fwd_dirs<bf16_t>(a, al, s);
-    return launch_fwd_dirs<f16_t>(a, al, s);
-  }
-  if (p->itype == MC_DTYPE_F32) return launch_fwd_t<float>(a, aligned, s);
-  if (p->itype == MC_DTYPE_BF16) return launch_fwd_t<bf16_t>(a, aligned, s);
-  return launch_fwd_t<f16_t>(a, aligned, s);
+  // grouped directions, vector modes: a mirrored 16-B block is aligned only when seqlen % VI == 0
+  const bool al = aligned && (!dirs || p->seqlen % (16 / ib) == 0);
+  if (p->itype == MC_DTYPE_F32) return launch_fwd_t<float>(a, al, dirs, s);
+  if (p->itype == MC_DTYPE_BF16) return launch_fwd_t<bf16_t>(a, al, dirs, s);
+  return launch_fwd_t<f16_t>(a, al, dirs, s);
 }
 
 extern "C" int32_t mc_scan_fwd_kernel(const mc_scan_fwd_params* p) {

@@ -36,19 +36,10 @@ constexpr int kPCh = 32;   // channels per wave
 constexpr int kPN = 16;    // dstate
 constexpr int kPH = 8;     // states per lane
 constexpr int kPG = 4;     // positions per recurrence group (32 B of {dt, du} per row)
-// State pairs per lane whose decays use the packed-FMA exp2 polynomial instead of v_exp_f32 (A/B
-// lever, VERDICT r03: balance the transcendental and the packed pipes).  Measured: one pair of four
-// 3.20 ms, two 3.79 ms against 2.56-2.86 ms (profiles/r04/scan_fwd_exp_poly_ab.txt) -- v_exp_f32 does
-// not co-issue with the packed FMAs, and the polynomial costs 15 issue slots per two values: 0.
-#ifndef MC_FWD_POLY_PAIRS
-#define MC_FWD_POLY_PAIRS 0
-#endif
-// Output rows stored non-temporally (nt cache policy): L2 keeps the u / delta / z lines whose second
-// 64-B half the next chunk reads.  Interleaved C4 A/B 2.81-2.84 vs 2.83-2.86 ms; PMC writes 1.58 GB
-// (= the output) instead of 1.85 GB, reads 4.35 vs 4.56 GB raw (profiles/r04/scan_fwd_nt_store_ab.txt)
-#ifndef MC_FWD_NT_STORE
-#define MC_FWD_NT_STORE 1
-#endif
+// Tried, slower (git history, profiles/r04/scan_fwd_exp_poly_ab.txt): decays of one or two of the four
+// state pairs on a packed-FMA exp2 polynomial instead of v_exp_f32, to balance the transcendental and
+// the packed pipes: 3.20 ms / 3.79 ms against 2.56-2.86 ms at C4 -- v_exp_f32 does not
+// co-issue with the packed FMAs, and the polynomial costs 15 issue slots per two values.
 
 template <typename TI>
 struct PairLayout {
@@ -60,8 +51,9 @@ struct PairLayout {
   static constexpr int kBCBytes = kT * 2 * kPN * 4;
 };
 
-template <typename TI, bool kSP, int kMinW, bool kFine>
-__global__ __launch_bounds__(64, kMinW) void scan_fwd_pair_kernel(const FwdArgs a) {
+// 3 waves per SIMD (16-bit rows only: fp32 rows double the staging registers and spill at that occupancy)
+template <typename TI, bool kSP, bool kFine>
+__global__ __launch_bounds__(64, 3) void scan_fwd_pair_kernel(const FwdArgs a) {
   using PL = PairLayout<TI>;
   constexpr int VI = PL::VI, kVPR = PL::kVPR, kNV = PL::kNV;
   static_assert(kT == 32 && kPN == 16 && VI == 8, "one 16-B B / C vector per lane and chunk");
@@ -231,8 +223,7 @@ __global__ __launch_bounds__(64, kMinW) void scan_fwd_pair_kernel(const FwdArgs 
 #pragma unroll
           for (int p = 0; p < kPH / 2; ++p) {
             const f32x2 arg = pk_mul_bcast<0>(A2[p], dtp);
-            if (p < MC_FWD_POLY_PAIRS) dA[p] = exp2_poly2(arg);   // A/B lever (default 0: all v_exp_f32)
-            else dA[p] = f32x2{fast_exp2(arg.x), fast_exp2(arg.y)};
+            dA[p] = f32x2{fast_exp2(arg.x), fast_exp2(arg.y)};
           }
           x[0] = pk_fma_bcast<0>(b0.lo, dup, dA[0] * x[0]);
           x[1] = pk_fma_bcast<0>(b0.hi, dup, dA[1] * x[1]);
@@ -298,8 +289,10 @@ __global__ __launch_bounds__(64, kMinW) void scan_fwd_pair_kernel(const FwdArgs 
           o[e + 1] = g.y;
         }
       }
-      if constexpr (MC_FWD_NT_STORE) buf_st16_nt(rs_o, voff(k, a.o_ds, l0) | ob, pack_f<TI>(o));
-      else buf_st16(rs_o, voff(k, a.o_ds, l0) | ob, pack_f<TI>(o));
+      // non-temporal: L2 keeps the u / delta / z lines whose second 64-B half the next chunk reads.  Interleaved
+      // C4 A/B against a plain store 2.81-2.84 vs 2.83-2.86 ms; PMC writes 1.58 GB (= the output) instead of
+      // 1.85 GB, reads 4.35 vs 4.56 GB raw (profiles/r04/scan_fwd_nt_store_ab.txt)
+      buf_st16_nt(rs_o, voff(k, a.o_ds, l0) | ob, pack_f<TI>(o));
     }
     wave_lds_sync();   // next chunk's staging overwrites the rows
   }
@@ -325,7 +318,7 @@ bool fwd_pair_ok(const FwdArgs& a, bool aligned, int itype_bytes, int itype, int
          bc(a.C, a.C_bs, a.C_gs, a.C_ns);
 }
 
-template <typename TI, int kMinW>
+template <typename TI>
 static int launch_pair_t(const FwdArgs& a0, hipStream_t s) {
   FwdArgs a = a0;
   const int H = a.dim / a.n_groups;
@@ -334,24 +327,23 @@ static int launch_pair_t(const FwdArgs& a0, hipStream_t s) {
   const size_t lds = (size_t)PairLayout<TI>::kRowBytes + PairLayout<TI>::kBCBytes;
   const dim3 grid(a.total_blocks), block(64);
   if (a.chunk_states && a.state_interval == kFineS) {   // training forward saving fine states
-    if (a.softplus) hipLaunchKernelGGL((scan_fwd_pair_kernel<TI, true, kMinW, true>), grid, block, lds, s, a);
-    else hipLaunchKernelGGL((scan_fwd_pair_kernel<TI, false, kMinW, true>), grid, block, lds, s, a);
+    if (a.softplus) hipLaunchKernelGGL((scan_fwd_pair_kernel<TI, true, true>), grid, block, lds, s, a);
+    else hipLaunchKernelGGL((scan_fwd_pair_kernel<TI, false, true>), grid, block, lds, s, a);
   } else {
-    if (a.softplus) hipLaunchKernelGGL((scan_fwd_pair_kernel<TI, true, kMinW, false>), grid, block, lds, s, a);
-    else hipLaunchKernelGGL((scan_fwd_pair_kernel<TI, false, kMinW, false>), grid, block, lds, s, a);
+    if (a.softplus) hipLaunchKernelGGL((scan_fwd_pair_kernel<TI, true, false>), grid, block, lds, s, a);
+    else hipLaunchKernelGGL((scan_fwd_pair_kernel<TI, false, false>), grid, block, lds, s, a);
   }
   const hipError_t e = hipGetLastError();
   MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "mc_scan_fwd: launch failed: %s", hipGetErrorString(e));
   return MC_OK;
 }
 
-// 16-bit rows only (fp32 rows double the staging registers and spill at 3 waves / SIMD).
-// Measured alternatives (interleaved on one box, C4 ms; built under tools/ for A/B runs):
+// Measured alternatives (interleaved on one box, C4 ms; the variants are in git history):
 // median softplus 2.82, the same at 4 waves/SIMD (spills) 3.59, log1p softplus 2.80,
 // + op_sel broadcasts of dt / du in inline asm (this kernel) 2.78; one-channel kernel 3.26.
 int launch_fwd_pair(const FwdArgs& a, int itype, hipStream_t s) {
-  if (itype == MC_DTYPE_BF16) return launch_pair_t<bf16_t, 3>(a, s);
-  return launch_pair_t<f16_t, 3>(a, s);
+  if (itype == MC_DTYPE_BF16) return launch_pair_t<bf16_t>(a, s);
+  return launch_pair_t<f16_t>(a, s);
 }
 
 }  // namespace scan

@@ -2,8 +2,8 @@
 
 * No packed-fp32 op with op_sel[src] = 1 (the low result reading a source's high half) in any kernel of
   scan_fwd_pair.hip / scan_bwd_pair.hip: that form, issued from inline asm, made the two-stream
-  training step non-reproducible; scan_common.h rejects it at compile time in our own
-  helpers and this test also catches the compiler choosing it.
+  training step non-reproducible; the form no longer exists in our own helpers
+  (scan_common.h), and this test also catches the compiler choosing it.
 * The fine-state backward instances (the C2 / C4 training path) and every forward pair instance run
   without VGPR spills.
 """

@@ -81,6 +81,10 @@ CASES = [
     (2, 96, 1024, 16, 2, torch.bfloat16, torch.bfloat16, True, False),     # H=48: a full + a half block
     (1, 80, 544, 16, 1, torch.float16, torch.float32, False, False),       # 17 chunks, no z, H=80
     (2, 64, 1000, 16, 1, torch.bfloat16, torch.bfloat16, True, False),     # last chunk runs past L (masked)
+    # L > 512 with fp32 B/C (the pair kernel declines): the LDS-staged one-channel kernel's other row modes
+    # (L = 544 above is its whole-chunk mode)
+    (1, 64, 520, 16, 1, torch.float16, torch.float32, True, False),        # aligned rows, ragged last chunk
+    (1, 64, 515, 16, 1, torch.float16, torch.float32, True, False),        # element-wise rows
 ]
 
 
