@@ -6,6 +6,8 @@
  * Mamba block: SURVEY.md section 2.2); the build owns them:
  *   mc_add_rmsnorm_fwd/bwd  fused residual-add + RMSNorm (Mamba block pre-norm,
  *                           residual stream kept in fp32)
+ *   mc_last_token_rmsnorm_fwd/bwd the same norm on one row per caption, the last non-pad
+ *                           token's (the Mamba text tower's pooling on padded captions)
  *   mc_add_layernorm_fwd/bwd fused residual-add + LayerNorm (ViT / BERT pre-LN
  *                           blocks: timm Block norm1/norm2 + the residual add)
  *   mc_causal_conv1d_fwd/bwd depthwise causal conv1d (+ optional SiLU) over the
@@ -45,6 +47,27 @@ int mc_add_rmsnorm_bwd(int32_t rows, int32_t cols, int32_t dtype, const void* dy
                        const float* w, const float* rstd, void* dx, float* dres_in, float* dw, void* workspace,
                        size_t workspace_bytes, void* stream);
 size_t mc_add_rmsnorm_bwd_workspace_bytes(int32_t rows, int32_t cols);
+
+/* Last-token add + RMSNorm: the Mamba text tower's final norm on the pooled row of each caption
+ * (transformers.MambaModel's norm_f at the last real token; a causal tower needs no masking inside
+ * its layers, only the right row).
+ *   pos[b] = max{t < T : tokens[b, t] != pad_id}, 0 when the whole row is pad (all 64 bits compared);
+ *   h = x[b, pos[b]] + res_in[b, pos[b]];  y[b] = h * rsqrt(mean(h^2) + eps) * w   (mc_add_rmsnorm_fwd's
+ *   arithmetic and dtype rules).
+ * tokens (batch, T) int64 contiguous; x (batch, Lp, cols) in dtype, Lp >= T; res_in fp32, same shape,
+ * nullable; y (batch, cols) dtype; h_out (batch, cols) fp32; rstd (batch,) fp32; pos (batch,) int32.
+ * One workgroup per caption.  cols as mc_add_rmsnorm_fwd; 16-B aligned buffers. */
+int mc_last_token_rmsnorm_fwd(int32_t batch, int32_t T, int32_t Lp, int32_t cols, int32_t dtype, const int64_t* tokens,
+                              int64_t pad_id, const void* x, const float* res_in, const float* w, float eps, void* y,
+                              float* h_out, float* rstd, int32_t* pos, void* stream);
+
+/* Backward given dy (batch, cols) in dtype and the forward's h, rstd, pos: ONE launch writes all of
+ * dx (batch, Lp, cols; dtype) and dres_in (fp32, nullable): row pos[b] = rstd * (w dy - h rstd^2 mean(h w dy)),
+ * every other row exact zeros (no separate memset); dw (cols,) fp32 = sum_b dy h rstd, the captions
+ * added in order by one thread per column (deterministic, no atomics, no workspace). */
+int mc_last_token_rmsnorm_bwd(int32_t batch, int32_t Lp, int32_t cols, int32_t dtype, const void* dy, const float* h,
+                              const float* w, const float* rstd, const int32_t* pos, void* dx, float* dres_in,
+                              float* dw, void* stream);
 
 /* Residual-add + LayerNorm (ViT / BERT pre-LN blocks):
  *   h = x + res (rounded to dtype; res nullable -> h = x), y = (h - mean) * rstd * w + bias.

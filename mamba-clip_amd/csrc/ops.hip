@@ -222,6 +222,162 @@ __global__ __launch_bounds__(256) void add_rmsnorm_bwd_kernel(int rows, int cols
   block_fold_store<NV, V>(dwacc, lane, nvec, dw_part + (int64_t)blockIdx.x * cols);
 }
 
+// ------------------------------------------------------------------ last-token add + RMSNorm
+// The Mamba text tower's final norm on the pooled row only: one workgroup per caption finds the
+// last position whose token is not pad_id (all 64 bits compared; 0 when the whole row is pad) and
+// its wave 0 normalises that one row of x (+ res_in) with add_rmsnorm_fwd_kernel's arithmetic.
+template <typename T, int NV>
+__global__ __launch_bounds__(256) void last_token_rmsnorm_fwd_kernel(int T_, int Lp, int cols,
+                                                                     const int64_t* __restrict__ tokens, int64_t pad_id,
+                                                                     const T* __restrict__ x,
+                                                                     const float* __restrict__ res_in,
+                                                                     const float* __restrict__ w, float eps,
+                                                                     T* __restrict__ y, float* __restrict__ h_out,
+                                                                     float* __restrict__ rstd, int* __restrict__ pos) {
+  constexpr int V = ElemTraits<T>::kVec;
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x;
+  const int nvec = cols / V;
+  const int64_t* __restrict__ tok = tokens + (int64_t)b * T_;
+  int last = 0;   // t ascends per thread: the thread's last hit is its maximum
+  for (int t = threadIdx.x; t < T_; t += 256)
+    if (tok[t] != pad_id) last = t;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) last = max(last, __shfl_xor(last, o, 64));
+  __shared__ int wave_last[4];
+  if (lane == 0) wave_last[threadIdx.x >> 6] = last;
+  __syncthreads();
+  if (threadIdx.x >= 64) return;
+  const int p = max(max(wave_last[0], wave_last[1]), max(wave_last[2], wave_last[3]));   // < T_ <= Lp
+  if (lane == 0) pos[b] = p;
+  const int64_t src = ((int64_t)b * Lp + p) * cols, dst = (int64_t)b * cols;
+  float h[NV][V], wr[NV][V];
+  float ss = 0.f;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int v = lane + 64 * i;
+    if (v < nvec) {
+      ld_f32v<V>(w + v * V, wr[i]);
+      const uint4 q = ld16(x + src + v * V);
+      float r[V];
+#pragma unroll
+      for (int e = 0; e < V; ++e) r[e] = 0.f;
+      if (res_in) ld_f32v<V>(res_in + src + v * V, r);
+#pragma unroll
+      for (int e = 0; e < V; ++e) h[i][e] = elem_f<T>(q, e) + r[e];
+#pragma unroll
+      for (int e = 0; e < V; ++e) ss = fmaf(h[i][e], h[i][e], ss);
+    }
+  }
+  ss = wave_allsum(ss);
+  const float rs = rsqrtf(ss / cols + eps);
+  if (lane == 0) rstd[b] = rs;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int v = lane + 64 * i;
+    if (v < nvec) {
+      float o[V];
+#pragma unroll
+      for (int e = 0; e < V; ++e) o[e] = h[i][e] * rs * wr[i][e];
+      st16(y + dst + v * V, pack_f<T>(o));
+      st_f32v<V>(h_out + dst + v * V, h[i]);
+    }
+  }
+}
+
+// Backward in one launch.  Blocks [0, row_blocks): one wave per row of the (batch * Lp, cols)
+// gradients, grid-stride; row pos[b] of caption b gets add_rmsnorm_bwd_kernel's dh, every other
+// row zeros (a pos outside [0, Lp) matches no row: nothing is addressed through it).  Blocks from
+// row_blocks on: dw, one thread per 16-B vector of columns, the captions added in order b = 0, 1, ...
+template <typename T, int NV>
+__global__ __launch_bounds__(256) void last_token_rmsnorm_bwd_kernel(int batch, int Lp, int cols, int row_blocks,
+                                                                     const T* __restrict__ dy,
+                                                                     const float* __restrict__ hbuf,
+                                                                     const float* __restrict__ w,
+                                                                     const float* __restrict__ rstd,
+                                                                     const int* __restrict__ pos, T* __restrict__ dx,
+                                                                     float* __restrict__ dres_in,
+                                                                     float* __restrict__ dw) {
+  constexpr int V = ElemTraits<T>::kVec;
+  const int nvec = cols / V;
+  if ((int)blockIdx.x >= row_blocks) {
+    const int v = ((int)blockIdx.x - row_blocks) * 256 + threadIdx.x;
+    if (v >= nvec) return;
+    float acc[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) acc[e] = 0.f;
+    for (int b = 0; b < batch; ++b) {
+      const int64_t off = (int64_t)b * cols + v * V;
+      const uint4 q = ld16(dy + off);
+      const float rs = rstd[b];
+      float hr[V];
+      ld_f32v<V>(hbuf + off, hr);
+#pragma unroll
+      for (int e = 0; e < V; ++e) acc[e] = fmaf(elem_f<T>(q, e), hr[e] * rs, acc[e]);
+    }
+    st_f32v<V>(dw + v * V, acc);
+    return;
+  }
+  const int lane = threadIdx.x & 63;
+  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int nwaves = (row_blocks * blockDim.x) >> 6;
+  const int rows = batch * Lp;
+  float wr[NV][V];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int v = lane + 64 * i;
+    if (v < nvec) ld_f32v<V>(w + v * V, wr[i]);
+  }
+  for (int row = wave; row < rows; row += nwaves) {
+    const int b = row / Lp;
+    const int64_t out = (int64_t)row * cols;
+    if (row - b * Lp != pos[b]) {   // wave-uniform
+      float z[V];
+#pragma unroll
+      for (int e = 0; e < V; ++e) z[e] = 0.f;
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int v = lane + 64 * i;
+        if (v < nvec) {
+          st16(dx + out + v * V, make_uint4(0u, 0u, 0u, 0u));
+          if (dres_in) st_f32v<V>(dres_in + out + v * V, z);
+        }
+      }
+      continue;
+    }
+    const float rs = rstd[b];
+    float h[NV][V], g[NV][V];
+    float dot = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int v = lane + 64 * i;
+      if (v < nvec) {
+        const int64_t off = (int64_t)b * cols + v * V;
+        const uint4 q = ld16(dy + off);
+        ld_f32v<V>(hbuf + off, h[i]);
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+          g[i][e] = elem_f<T>(q, e) * wr[i][e];
+          dot = fmaf(g[i][e], h[i][e], dot);
+        }
+      }
+    }
+    dot = wave_allsum(dot);
+    const float c = dot * rs * rs / cols;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int v = lane + 64 * i;
+      if (v < nvec) {
+        float o[V];
+#pragma unroll
+        for (int e = 0; e < V; ++e) o[e] = rs * (g[i][e] - h[i][e] * c);
+        st16(dx + out + v * V, pack_f<T>(o));
+        if (dres_in) st_f32v<V>(dres_in + out + v * V, o);
+      }
+    }
+  }
+}
+
 // Deterministic column sums of a row-major partial slab in two passes:
 //   pass 1: grid (ceil(cols/256), kColSlices); thread = one column over a
 //           fixed row slice (coalesced across the block) -> tmp[slice][c]
@@ -1094,6 +1250,50 @@ extern "C" int mc_add_rmsnorm_bwd(int32_t rows, int32_t cols, int32_t dtype, con
       dim3(kNormGrid), dim3(256), 0, s, rows, cols, (const T*)dy, dres, h, w, rstd, (T*)dx, dres_in, part)));
   colsum_two_pass(part, kNormGrid, cols, cols, dw, nullptr, part + (size_t)kNormGrid * 4 * cols, s);
   return check_launch("mc_add_rmsnorm_bwd");
+}
+
+extern "C" int mc_last_token_rmsnorm_fwd(int32_t batch, int32_t ntok, int32_t Lp, int32_t cols, int32_t dtype,
+                                         const int64_t* tokens, int64_t pad_id, const void* x, const float* res_in,
+                                         const float* w, float eps, void* y, float* h_out, float* rstd, int32_t* pos,
+                                         void* stream) {
+  MC_CHECK(dtype >= MC_DTYPE_F32 && dtype <= MC_DTYPE_F16, MC_ERR_DTYPE, "mc_last_token_rmsnorm_fwd: bad dtype");
+  const int V = dtype == MC_DTYPE_F32 ? 4 : 8;
+  MC_CHECK(cols > 0 && cols % V == 0 && cols / V <= 64 * kMaxVec, MC_ERR_SHAPE,
+           "mc_last_token_rmsnorm_fwd: cols=%d must be a multiple of %d and <= %d", cols, V, 64 * kMaxVec * V);
+  MC_CHECK(batch >= 0 && ntok >= 1 && Lp >= ntok, MC_ERR_SHAPE,
+           "mc_last_token_rmsnorm_fwd: batch=%d, T=%d, Lp=%d: need batch >= 0 and 1 <= T <= Lp", batch, ntok, Lp);
+  if (batch == 0) return MC_OK;
+  MC_CHECK(tokens && x && w && y && h_out && rstd && pos, MC_ERR_INVALID,
+           "mc_last_token_rmsnorm_fwd: tokens, x, w, y, h_out, rstd, pos required");
+  MC_CHECK(aligned16(x) && aligned16(res_in) && aligned16(w) && aligned16(y) && aligned16(h_out), MC_ERR_INVALID,
+           "mc_last_token_rmsnorm_fwd: x, res_in, w, y, h_out must be 16-B aligned");
+  MC_DISPATCH_T(dtype, MC_DISPATCH_NV(norm_nv(cols, V), hipLaunchKernelGGL((last_token_rmsnorm_fwd_kernel<T, NV>),
+      dim3(batch), dim3(256), 0, (hipStream_t)stream, ntok, Lp, cols, tokens, pad_id, (const T*)x, res_in, w, eps, (T*)y,
+      h_out, rstd, pos)));
+  return check_launch("mc_last_token_rmsnorm_fwd");
+}
+
+extern "C" int mc_last_token_rmsnorm_bwd(int32_t batch, int32_t Lp, int32_t cols, int32_t dtype, const void* dy,
+                                         const float* h, const float* w, const float* rstd, const int32_t* pos,
+                                         void* dx, float* dres_in, float* dw, void* stream) {
+  MC_CHECK(dtype >= MC_DTYPE_F32 && dtype <= MC_DTYPE_F16, MC_ERR_DTYPE, "mc_last_token_rmsnorm_bwd: bad dtype");
+  const int V = dtype == MC_DTYPE_F32 ? 4 : 8;
+  MC_CHECK(cols > 0 && cols % V == 0 && cols / V <= 64 * kMaxVec, MC_ERR_SHAPE,
+           "mc_last_token_rmsnorm_bwd: bad cols=%d", cols);
+  MC_CHECK(batch >= 0 && Lp >= 1 && (int64_t)batch * Lp <= INT32_MAX, MC_ERR_SHAPE,
+           "mc_last_token_rmsnorm_bwd: batch=%d, Lp=%d: need batch >= 0, Lp >= 1 and batch * Lp < 2^31", batch, Lp);
+  MC_CHECK(dw && aligned16(dw), MC_ERR_INVALID, "mc_last_token_rmsnorm_bwd: dw required (16-B aligned)");
+  MC_CHECK(batch == 0 || (dy && h && w && rstd && pos && dx), MC_ERR_INVALID,
+           "mc_last_token_rmsnorm_bwd: dy, h, w, rstd, pos, dx required");
+  MC_CHECK(aligned16(dy) && aligned16(h) && aligned16(w) && aligned16(dx) && aligned16(dres_in), MC_ERR_INVALID,
+           "mc_last_token_rmsnorm_bwd: dy, h, w, dx, dres_in must be 16-B aligned");
+  const int rows = batch * Lp;
+  const int row_blocks = std::min((rows + 3) / 4, 2048);
+  const int dw_blocks = (cols / V + 255) / 256;
+  MC_DISPATCH_T(dtype, MC_DISPATCH_NV(norm_nv(cols, V), hipLaunchKernelGGL((last_token_rmsnorm_bwd_kernel<T, NV>),
+      dim3(row_blocks + dw_blocks), dim3(256), 0, (hipStream_t)stream, batch, Lp, cols, row_blocks, (const T*)dy, h, w,
+      rstd, pos, (T*)dx, dres_in, dw)));
+  return check_launch("mc_last_token_rmsnorm_bwd");
 }
 
 extern "C" int mc_add_layernorm_fwd(int32_t rows, int32_t cols, int32_t dtype, const void* x, const void* res,

@@ -310,6 +310,10 @@ SYMBOLS = {
     "mc_add_rmsnorm_bwd": (ctypes.c_int, [c_i32, c_i32, c_i32, c_vp, c_fp, c_fp, c_fp, c_fp, c_vp, c_fp, c_fp, c_vp,
                                           ctypes.c_size_t, c_vp]),
     "mc_add_rmsnorm_bwd_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32]),
+    "mc_last_token_rmsnorm_fwd": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_fp, c_fp,
+                                                 ctypes.c_float, c_vp, c_fp, c_fp, c_vp, c_vp]),
+    "mc_last_token_rmsnorm_bwd": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, c_vp, c_fp, c_fp, c_fp, c_vp, c_vp, c_fp,
+                                                 c_fp, c_vp]),
     "mc_add_layernorm_fwd": (ctypes.c_int, [c_i32, c_i32, c_i32, c_vp, c_vp, c_fp, c_fp, ctypes.c_float, c_vp, c_vp,
                                             c_fp, c_fp, c_vp]),
     "mc_add_layernorm_bwd": (ctypes.c_int, [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_fp, c_fp, c_fp, c_vp, c_fp, c_fp,

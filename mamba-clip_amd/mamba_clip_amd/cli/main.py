@@ -47,7 +47,8 @@ def build_parser():
     p.add_argument("--model", type=str, default="vit_b16-mamba130m",
                    help="stage-1 model config (offline: vit_b16-mamba130m, tiny-mamba-clip, mamba790m-text, "
                         "biomedclip-vit_b16-pubmedbert256, biomedclip-vit_b16-pubmedbert256-hf: the text "
-                        "tower that computes HF BertModel)")
+                        "tower that computes HF BertModel, vit_b16-mamba130m-hf: the Mamba tower pooled at each "
+                        "caption's last non-pad token, HF MambaModel)")
     p.add_argument("--model-stage-1", type=str, default=None, help="alias of --model for stage 2")
     p.add_argument("--model-stage-2", type=str, default="ClipClassifier")
     p.add_argument("--use-inner-prod", action="store_true")
@@ -72,6 +73,9 @@ def build_parser():
                    help="evaluate every this many epochs and after the last one (0: never)")
     p.add_argument("--val-num-samples", type=int, default=None,
                    help="validation samples (synthetic: distinct batches; default 4 batches)")
+    p.add_argument("--text-min-len", type=int, default=None,
+                   help="synthetic captions of lengths in [this, context length], end-of-text last, pad id 0 "
+                        "behind (default: every caption fills the context)")
     return p
 
 
@@ -144,7 +148,7 @@ def main(argv=None):
         val_batches = max(1, (args.val_num_samples or 4 * args.batch_size) // args.batch_size)
     data = get_synthetic_data(args.batch_size, n_batches, img_size, text.context_length, text.vocab_size, device,
                               seed=1000 + args.rank, balanced=args.balanced_mixup is not None,
-                              num_classes=args.num_classes, val_batches=val_batches)
+                              num_classes=args.num_classes, val_batches=val_batches, text_min_len=args.text_min_len)
     total_steps = n_batches // args.accum_freq * args.epochs
     scheduler = _make_scheduler(optimizer, args, total_steps)
 

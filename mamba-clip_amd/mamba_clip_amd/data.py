@@ -10,7 +10,8 @@ training and the bench consume (images, texts, targets) of the right shapes and 
     buffers on a copy stream; ToTensor + Normalize run on the device, fused into the towers' patch
     embedding (ops.patch_im2col -> mc_patch_embed_input), so the PCIe copy is 4x smaller than the
     reference's normalised fp32 batch.
-Text rows end with the end-of-text token at the last position (pooling index).
+Text rows end with the end-of-text token at the last position (pooling index); with text_min_len each
+caption has a length of its own, its end-of-text id at its last real position and pad id 0 after it.
 """
 import queue
 import threading
@@ -19,9 +20,23 @@ from dataclasses import dataclass
 import torch
 
 
+def pad_captions(texts, text_min_len, eot_id, generator):
+    """In place: a length per row drawn from [text_min_len, context_length], eot_id at its last real
+    position, pad id 0 behind it (right padding)."""
+    n, ctx = texts.shape
+    if not 1 <= text_min_len <= ctx:
+        raise ValueError(f"text_min_len={text_min_len} must lie in [1, {ctx}]")
+    lengths = torch.randint(text_min_len, ctx + 1, (n,), generator=generator)
+    texts.masked_fill_(torch.arange(ctx)[None, :] >= lengths[:, None], 0)
+    texts[torch.arange(n), lengths - 1] = eot_id
+    return texts
+
+
 def synthetic_batch(batch, image_size, context_length, vocab_size, num_classes=2, device="cpu", seed=0,
-                    image_dtype=torch.float32):
-    """image_dtype float: (B, 3, S, S) N(0, 1) (a normalised batch); torch.uint8: (B, S, S, 3) raw bytes."""
+                    image_dtype=torch.float32, text_min_len=None):
+    """image_dtype float: (B, 3, S, S) N(0, 1) (a normalised batch); torch.uint8: (B, S, S, 3) raw bytes.
+    text_min_len: caption lengths from [text_min_len, context_length] (drawn after everything else, so
+    None consumes the generator as before), end-of-text last, pad 0 behind."""
     g = torch.Generator(device="cpu").manual_seed(seed)
     if image_dtype == torch.uint8:
         images = torch.randint(0, 256, (batch, image_size, image_size, 3), dtype=torch.uint8, generator=g).to(device)
@@ -30,6 +45,8 @@ def synthetic_batch(batch, image_size, context_length, vocab_size, num_classes=2
     texts = torch.randint(1, vocab_size - 1, (batch, context_length), generator=g)
     texts[:, -1] = vocab_size - 1                               # end-of-text id at the pooled position
     targets = torch.randint(0, num_classes, (batch,), generator=g)
+    if text_min_len is not None:
+        pad_captions(texts, text_min_len, vocab_size - 1, g)
     return images, texts.to(device), targets.to(device)
 
 
@@ -79,11 +96,14 @@ class DataInfo:
 
 
 def get_synthetic_data(batch, num_batches, image_size, context_length, vocab_size, device, seed=0,
-                       image_dtype=torch.float32, balanced=False, num_classes=2, val_batches=0, val_seed=None):
+                       image_dtype=torch.float32, balanced=False, num_classes=2, val_batches=0, val_seed=None,
+                       text_min_len=None):
     """{"train": DataInfo}; with val_batches > 0 also {"val": DataInfo} of that many DISTINCT batches
     (seeds val_seed + i, default seed + 500000 + i)."""
     kw = dict(image_size=image_size, context_length=context_length, vocab_size=vocab_size, num_classes=num_classes,
               device=device, image_dtype=image_dtype)
+    if text_min_len is not None:
+        kw["text_min_len"] = text_min_len
     data = {"train": DataInfo(_SyntheticLoader(batch, num_batches, balanced=balanced, seed=seed, **kw))}
     if val_batches > 0:
         vs = seed + 500000 if val_seed is None else val_seed
@@ -109,12 +129,14 @@ class IsicShapedDataset:
     contiguous tensors, indexable per sample like a torch Dataset."""
 
     def __init__(self, num_samples, image_size=224, context_length=77, vocab_size=50000, positive_fraction=0.01,
-                 seed=0):
+                 seed=0, text_min_len=None):
         g = torch.Generator().manual_seed(seed)
         self.images = torch.randint(0, 256, (num_samples, image_size, image_size, 3), dtype=torch.uint8, generator=g)
         self.texts = torch.randint(1, vocab_size - 1, (num_samples, context_length), generator=g)
         self.texts[:, -1] = vocab_size - 1
         self.targets = (torch.rand(num_samples, generator=g) < positive_fraction).long()
+        if text_min_len is not None:   # drawn last: None consumes the generator as before
+            pad_captions(self.texts, text_min_len, vocab_size - 1, g)
 
     def __len__(self):
         return self.images.shape[0]
@@ -218,6 +240,6 @@ class HostToDeviceLoader:
 
 
 def get_isic_shaped_data(batch, num_samples, image_size, context_length, vocab_size, device, rank=0, world_size=1,
-                         seed=0, positive_fraction=0.01):
-    ds = IsicShapedDataset(num_samples, image_size, context_length, vocab_size, positive_fraction, seed)
+                         seed=0, positive_fraction=0.01, text_min_len=None):
+    ds = IsicShapedDataset(num_samples, image_size, context_length, vocab_size, positive_fraction, seed, text_min_len)
     return {"train": DataInfo(HostToDeviceLoader(ds, batch, device, rank, world_size, seed))}

@@ -14,7 +14,8 @@ SURVEY.md 8c) are defined here and random-initialised:
   VisionTransformer  ViT-B/16 (timm vit_base_patch16_224 shape: 12 pre-LN
                      blocks, 768 wide, cls pooling, proj -> embed_dim)
   MambaTextEncoder   Mamba LM text tower (Mamba-130M: 24 x d_model 768,
-                     d_inner 1536, d_state 16, RMSNorm, fp32 residual stream)
+                     d_inner 1536, d_state 16, RMSNorm, fp32 residual stream); with pad_id it
+                     pools each caption's last token and computes transformers.MambaModel
   BertTextEncoder    PubMedBERT-base shape (12 x 768, ctx 256) for BiomedCLIP
   HFBertTextEncoder  the same tower computing transformers.BertModel (post-LN, token types, padding mask)
 Hot ops run on the HIP library: selective scan, causal conv1d, fused
@@ -34,9 +35,10 @@ import torch.utils.checkpoint
 
 from . import GEMM_GRIDS_DATA_PARALLEL
 from .ops import (GradHandoff, GradSlab, _compute_dtype, add_layernorm, add_pos, add_rmsnorm, attn_supported,
-                  causal_conv1d, l2_normalize, linear_sk, mixer_proj, mixer_proj_ok, mlp, neg_exp_many,
-                  pack_key_mask, packed_attention, patch_im2col, qkv_proj, split_rows, split_rows_n, ss2d_conv_stack,
-                  ss2d_merge_ln_gate, ss2d_proj, ss2d_proj_ok, token_embed, weight_cast_scope, wleft_mm)
+                  causal_conv1d, l2_normalize, last_token_rmsnorm, linear_sk, mixer_proj, mixer_proj_ok, mlp,
+                  neg_exp_many, pack_key_mask, packed_attention, patch_im2col, qkv_proj, split_rows, split_rows_n,
+                  ss2d_conv_stack, ss2d_merge_ln_gate, ss2d_proj, ss2d_proj_ok, token_embed, weight_cast_scope,
+                  wleft_mm)
 from .selective_scan_interface import (SS2D_REVERSE_GROUPS, SS2D_U_GROUPS, SelectiveScanFn, fine_state_scope,
                                        grouped_scan_fn, selective_scan_fn)
 
@@ -158,17 +160,26 @@ class MambaLayer(nn.Module):
 class MambaTextEncoder(nn.Module):
     """Mamba LM text tower for CLIP: tokens (B, T) int64 -> (B, output_dim).
 
-    Pools the hidden state at the end-of-text position (the last position, as
-    the synthetic tokens put EOT there: SURVEY 8d).  The sequence is padded to
-    a multiple of 8 positions after the real tokens (causal: padding never
+    pad_id=None (the default): pools the hidden state at the last position T - 1, where the
+    synthetic tokens put end-of-text; right only for captions as long as the context.
+    pad_id=<int>: pools at each caption's last token that is not pad_id, through the last-token
+    add + RMSNorm kernel (ops.last_token_rmsnorm) -- transformers.MambaModel's hidden row len - 1.
+    The tower is causal, so the layers need no masking: padding behind a caption never reaches its
+    rows.  Right padding only (left padding would put pad tokens in front of the caption, inside
+    its history); pad ids inside a caption are allowed, the search is for the LAST non-pad token; a
+    row of nothing but pad pools position 0.  load_hf_mamba_state_dict fills the tower from an
+    HF-named state dict; tests/golden/mamba_hf_tiny*.safetensors pin it to transformers.
+
+    The sequence is padded to a multiple of 8 positions after the real tokens (causal: padding never
     reaches earlier positions) so every activation row is 16-B aligned.
     """
 
     def __init__(self, vocab_size=50280, context_length=77, d_model=768, n_layer=24, d_state=16,
-                 output_dim=512):
+                 output_dim=512, pad_id=None):
         super().__init__()
         self.vocab_size, self.context_length, self.d_model = vocab_size, context_length, d_model
         self.output_dim = output_dim
+        self.pad_id = None if pad_id is None else int(pad_id)
         self.embedding = nn.Embedding(vocab_size, d_model)
         nn.init.normal_(self.embedding.weight, std=0.02)
         self.layers = nn.ModuleList([MambaLayer(d_model, d_state) for _ in range(n_layer)])
@@ -182,9 +193,11 @@ class MambaTextEncoder(nn.Module):
                 [list(l.named_parameters(prefix=f"layers.{i}")) for i, l in enumerate(self.layers)],
                 [("norm_f", self.norm_f)])
 
-    def forward(self, tokens):
+    def forward_hidden(self, tokens):
+        """The pooled row after the final norm, (B, d_model): what `proj` projects."""
         Bsz, T = tokens.shape
         Lp = (T + 7) // 8 * 8
+        given = tokens
         if Lp != T:
             tokens = F.pad(tokens, (0, Lp - T))
         dt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else torch.float32
@@ -206,9 +219,17 @@ class MambaTextEncoder(nn.Module):
                 hidden, residual = torch.utils.checkpoint.checkpoint(run, layer, hidden, residual, A, use_reentrant=False)
             else:
                 hidden, residual = run(layer, hidden, residual, A)
+        if self.pad_id is not None:
+            # the final norm on the pooled rows only, at each caption's last non-pad token of the T given
+            return last_token_rmsnorm(given, self.pad_id, hidden, residual, self.norm_f)[0]
         normed, _ = add_rmsnorm(hidden, residual, self.norm_f)
-        pooled = normed[:, T - 1]                                   # EOT position
-        return self.proj(pooled)
+        return normed[:, T - 1]                                     # EOT position
+
+    def forward(self, tokens):
+        return self.proj(self.forward_hidden(tokens))
+
+    def load_hf_mamba_state_dict(self, sd):
+        return load_hf_mamba_state_dict(self, sd)
 
     grad_checkpointing = False
 
@@ -216,6 +237,37 @@ class MambaTextEncoder(nn.Module):
         """Activation checkpointing per Mamba layer (torch.utils.checkpoint, non-reentrant): the reference's
         ClipModel.set_grad_checkpointing (model.py:1099-1102) turns it on in open_clip's towers."""
         self.grad_checkpointing = bool(enable)
+
+
+_HF_MAMBA_MIXER = ("A_log", "D", "conv1d.weight", "conv1d.bias", "in_proj.weight", "x_proj.weight", "dt_proj.weight",
+                   "dt_proj.bias", "out_proj.weight")
+
+
+def load_hf_mamba_state_dict(model, sd):
+    """Copy a transformers MambaModel / MambaForCausalLM state dict (HF names, with or without a leading
+    "backbone.") into a MambaTextEncoder: embeddings.weight -> embedding.weight, layers.i.norm.weight ->
+    layers.i.norm_weight, layers.i.mixer.* under the same names, norm_f.weight -> norm_f.  Strict: a
+    missing or an unexpected key raises KeyError, a shape mismatch ValueError naming the tensor; only
+    lm_head.weight is ignored.  The projection after the pooled row is not part of the HF model and
+    keeps its values."""
+    sd = {(k[9:] if k.startswith("backbone.") else k): v for k, v in sd.items()}
+    sd = {k: v for k, v in sd.items() if k != "lm_head.weight"}
+    want = {"embeddings.weight": model.embedding.weight, "norm_f.weight": model.norm_f}
+    for i, layer in enumerate(model.layers):
+        want[f"layers.{i}.norm.weight"] = layer.norm_weight
+        for name in _HF_MAMBA_MIXER:
+            want[f"layers.{i}.mixer.{name}"] = layer.mixer.get_parameter(name)
+    missing, unexpected = sorted(set(want) - set(sd)), sorted(set(sd) - set(want))
+    if missing or unexpected:
+        raise KeyError(f"load_hf_mamba_state_dict: missing {missing}, unexpected {unexpected}")
+    for name, param in want.items():
+        if sd[name].shape != param.shape:
+            raise ValueError(f"load_hf_mamba_state_dict: {name} is {tuple(sd[name].shape)}, "
+                             f"the tower has {tuple(param.shape)}")
+    with torch.no_grad():
+        for name, param in want.items():
+            param.copy_(sd[name])
+    return model
 
 
 def _run_blocks(blocks, m, h, ckpt):
@@ -1023,6 +1075,10 @@ MODEL_CONFIGS = {
     # C2: ViT-B/16 + Mamba-130M text (BASELINE configs[1])
     "vit_b16-mamba130m": dict(vision=dict(), text=dict(vocab_size=50280, context_length=77, d_model=768,
                                                         n_layer=24, output_dim=512)),
+    # C2 with padded captions pooled at their last token (pad id 0): the tower state-spaces/mamba-130m-hf
+    # loads into (load_hf_mamba_state_dict)
+    "vit_b16-mamba130m-hf": dict(vision=dict(), text=dict(vocab_size=50280, context_length=77, d_model=768,
+                                                           n_layer=24, output_dim=512, pad_id=0)),
     # C4 text tower (BASELINE configs[3])
     "mamba790m-text": dict(vision=dict(), text=dict(vocab_size=50280, context_length=4096, d_model=1536,
                                                      n_layer=48, output_dim=512)),

@@ -437,6 +437,59 @@ def add_rmsnorm(x, residual, weight, eps=1e-5):
     return AddRMSNormFn.apply(x, residual, weight, eps)
 
 
+class LastTokenRMSNormFn(torch.autograd.Function):
+    """(y, pos): pos[b] = the last position of tokens[b] that is not pad_id (0 for an all-pad row),
+    y[b] = rmsnorm(x[b, pos[b]] + res[b, pos[b]]) * w.  The backward writes the whole of dx / dres
+    (zeros off the pooled rows) in its one launch (include/mc_ops.h, mc_last_token_rmsnorm_*)."""
+
+    @staticmethod
+    def forward(ctx, tokens, pad_id, x, res, weight, eps):
+        lib = _lib.load()
+        if tokens.dim() != 2 or tokens.dtype != torch.int64 or x.dim() != 3 or x.shape[0] != tokens.shape[0]:
+            raise RuntimeError("last_token_rmsnorm: tokens must be (B, T) int64 and x (B, Lp, cols)")
+        if res is not None and res.shape != x.shape:
+            raise RuntimeError("last_token_rmsnorm: residual must have x's shape")
+        tokens = tokens.contiguous()
+        x = x.contiguous()
+        Bsz, Lp, cols = x.shape
+        y = torch.empty(Bsz, cols, device=x.device, dtype=x.dtype)
+        h = torch.empty(Bsz, cols, device=x.device, dtype=torch.float32)
+        rstd = torch.empty(Bsz, device=x.device, dtype=torch.float32)
+        pos = torch.empty(Bsz, device=x.device, dtype=torch.int32)
+        w = weight.float().contiguous()
+        r = res.float().contiguous() if res is not None else None
+        _lib.check(lib.mc_last_token_rmsnorm_fwd(Bsz, tokens.shape[1], Lp, cols, _lib.dtype_code(x.dtype),
+                                                 tokens.data_ptr(), int(pad_id), x.data_ptr(), _lib.ptr(r),
+                                                 w.data_ptr(), float(eps), y.data_ptr(), h.data_ptr(),
+                                                 rstd.data_ptr(), pos.data_ptr(), _lib.stream_handle(x.device)),
+                   "mc_last_token_rmsnorm_fwd")
+        ctx.save_for_backward(h, w, rstd, pos)
+        ctx.meta = (x.dtype, res is not None, weight.dtype, Lp)
+        ctx.mark_non_differentiable(pos)
+        return y, pos
+
+    @staticmethod
+    def backward(ctx, dy, _dpos):
+        lib = _lib.load()
+        h, w, rstd, pos = ctx.saved_tensors
+        xdt, has_res, wdt, Lp = ctx.meta
+        Bsz, cols = h.shape
+        dy = dy.to(xdt).contiguous()
+        dx = torch.empty(Bsz, Lp, cols, device=h.device, dtype=xdt)
+        dres_in = torch.empty(Bsz, Lp, cols, device=h.device, dtype=torch.float32) if has_res else None
+        dw = torch.empty(cols, device=h.device, dtype=torch.float32)
+        _lib.check(lib.mc_last_token_rmsnorm_bwd(Bsz, Lp, cols, _lib.dtype_code(xdt), dy.data_ptr(), h.data_ptr(),
+                                                 w.data_ptr(), rstd.data_ptr(), pos.data_ptr(), dx.data_ptr(),
+                                                 _lib.ptr(dres_in), dw.data_ptr(), _lib.stream_handle(h.device)),
+                   "mc_last_token_rmsnorm_bwd")
+        return None, None, dx, dres_in, dw.to(wdt), None
+
+
+def last_token_rmsnorm(tokens, pad_id, x, residual, weight, eps=1e-5):
+    """(y, pos) of LastTokenRMSNormFn; pos (B,) int32 is not differentiable."""
+    return LastTokenRMSNormFn.apply(tokens, pad_id, x, residual, weight, eps)
+
+
 class AddLayerNormFn(torch.autograd.Function):
     """(y, h) = (LayerNorm(x + res) * w + b, x + res); h in the activation dtype (pre-LN residual stream)."""
 
