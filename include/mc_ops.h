@@ -220,45 +220,6 @@ typedef struct mc_adamw_hyper {
 int mc_adamw_step(int32_t n_chunks, const mc_adamw_chunk* chunks, const mc_adamw_tensor* tensors,
                   const mc_adamw_hyper* hyper, void* stream);
 
-/* ---- Mamba mixer projections (mixer_proj.hip): x_proj and dt_proj around the scan, fused.
- * Reference: the mixer's x_dbl = x_proj(x), delta = dt_proj.weight @ dt_raw (upstream
- * mamba_simple.Mamba; SS2D's analogue model.py:519-528, 630-647).  Channel-major activations
- * (dim, tokens), tokens contiguous; all 16-bit (dtype bf16 / f16), weights contiguous.
- *   forward:  x_dbl (P, T) = w_x (P, D) . x (D, T), rounded to dtype;
- *             delta (D, T) = w_dt (D, R) . x_dbl[0:R], rounded (no bias: the scan adds it)
- *   backward: d_x_dbl (P, T) = [w_dt^T . g_delta ; g_b ; g_c], rounded;
- *             dx (D, T) = w_x^T . d_x_dbl + du (du nullable), rounded once
- * The weight gradients are left to the caller (they are reductions over T).
- * Requirements: dim % 64 == 0, tokens % 8 == 0, rank % 16 == 0 in [16, 96], proj_rows = rank + 32
- * (dstate 16: every reference config); 16-B aligned rows (strides % 8 elements; du 8-B), w_dt
- * 8-B aligned. */
-typedef struct mc_mixer_proj_params {
-  int32_t dim, tokens, rank, proj_rows, dtype;
-  int64_t x_ld, x_dbl_ld, delta_ld;      /* row strides (elements) */
-  const void* x;                          /* (dim, tokens) */
-  const void* w_x;                        /* (proj_rows, dim): x_proj.weight */
-  const void* w_dt;                       /* (dim, rank): dt_proj.weight */
-  void* x_dbl;                            /* (proj_rows, tokens) out */
-  void* delta;                            /* (dim, tokens) out */
-} mc_mixer_proj_params;
-
-int mc_mixer_proj_fwd(const mc_mixer_proj_params* p, void* stream);
-
-typedef struct mc_mixer_proj_bwd_params {
-  int32_t dim, tokens, rank, proj_rows, dtype;
-  int64_t g_delta_ld, g_b_ld, g_c_ld, du_ld, d_x_dbl_ld, dx_ld;
-  const void* g_delta;                    /* (dim, tokens): gradient of delta */
-  const void* g_b;                        /* nullable (16, tokens): gradient of x_dbl's B rows (the scan's dB) */
-  const void* g_c;                        /* nullable (16, tokens): gradient of the C rows (dC) */
-  const void* w_x;
-  const void* w_dt;
-  const void* du;                         /* nullable (dim, tokens): the other consumer's gradient of x */
-  void* d_x_dbl;                          /* (proj_rows, tokens) out */
-  void* dx;                               /* (dim, tokens) out */
-} mc_mixer_proj_bwd_params;
-
-int mc_mixer_proj_bwd(const mc_mixer_proj_bwd_params* p, void* stream);
-
 /* mc_colsum: out[c] = sum_{r < rows} x[r * ld + c] in fp32, c < cols, x fp32 / bf16 / fp16 row-major
  * (row stride ld elements).  Fixed row slices summed per workgroup, the slice partials folded in order:
  * deterministic, and no workgroup reads another's results during the launch.  Replaces torch's batch /

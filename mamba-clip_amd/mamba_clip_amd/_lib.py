@@ -85,26 +85,6 @@ class AdamWHyper(ctypes.Structure):
     _fields_ = [("n_groups", ctypes.c_int32), ("reserved", ctypes.c_int32), ("group", AdamWGroup * MC_ADAMW_MAX_GROUPS)]
 
 
-class MixerProjParams(ctypes.Structure):
-    """Mirror of ``mc_mixer_proj_params`` (include/mc_ops.h)."""
-    _fields_ = [
-        ("dim", c_i32), ("tokens", c_i32), ("rank", c_i32), ("proj_rows", c_i32), ("dtype", c_i32),
-        ("x_ld", c_i64), ("x_dbl_ld", c_i64), ("delta_ld", c_i64),
-        ("x", c_vp), ("w_x", c_vp), ("w_dt", c_vp), ("x_dbl", c_vp), ("delta", c_vp),
-    ]
-
-
-class MixerProjBwdParams(ctypes.Structure):
-    """Mirror of ``mc_mixer_proj_bwd_params`` (include/mc_ops.h)."""
-    _fields_ = [
-        ("dim", c_i32), ("tokens", c_i32), ("rank", c_i32), ("proj_rows", c_i32), ("dtype", c_i32),
-        ("g_delta_ld", c_i64), ("g_b_ld", c_i64), ("g_c_ld", c_i64), ("du_ld", c_i64), ("d_x_dbl_ld", c_i64),
-        ("dx_ld", c_i64),
-        ("g_delta", c_vp), ("g_b", c_vp), ("g_c", c_vp), ("w_x", c_vp), ("w_dt", c_vp), ("du", c_vp),
-        ("d_x_dbl", c_vp), ("dx", c_vp),
-    ]
-
-
 class GemmNTParams(ctypes.Structure):
     """Mirror of ``mc_gemm_nt_params`` (include/mc_contrastive.h)."""
     _fields_ = [
@@ -283,7 +263,6 @@ SYMBOLS = {
     "mc_linear_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(LinearParams)]),
     "mc_linear": (ctypes.c_int, [ctypes.POINTER(LinearParams), c_vp]),
     "mc_gemm_small_k": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
-    "mc_gemm_skinny_m": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "mc_scan_bwd_kernel": (c_i32, [ctypes.POINTER(ScanBwdParams)]),
     "mc_scan_chunk_states_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32, c_i32]),
     "mc_scan_fwd_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32, c_i32]),
@@ -345,8 +324,6 @@ SYMBOLS = {
     "mc_attn_bwd": (ctypes.c_int, [ctypes.POINTER(AttnBwdParams), c_vp]),
     "mc_attn_masked_fwd": (ctypes.c_int, [ctypes.POINTER(AttnMaskedFwdParams), c_vp]),
     "mc_attn_masked_bwd": (ctypes.c_int, [ctypes.POINTER(AttnMaskedBwdParams), c_vp]),
-    "mc_mixer_proj_fwd": (ctypes.c_int, [ctypes.POINTER(MixerProjParams), c_vp]),
-    "mc_mixer_proj_bwd": (ctypes.c_int, [ctypes.POINTER(MixerProjBwdParams), c_vp]),
     "mc_patch_embed_input": (ctypes.c_int, [ctypes.POINTER(PatchInputParams), c_vp]),
     "mc_ss2d_conv_stack_fwd": (ctypes.c_int, [ctypes.POINTER(SS2DConvParams), c_vp]),
     "mc_ss2d_conv_stack_bwd": (ctypes.c_int, [ctypes.POINTER(SS2DConvBwdParams), c_vp]),

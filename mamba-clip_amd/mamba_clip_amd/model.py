@@ -35,10 +35,9 @@ import torch.utils.checkpoint
 
 from . import GEMM_GRIDS_DATA_PARALLEL
 from .ops import (GradHandoff, GradSlab, _compute_dtype, add_layernorm, add_pos, add_rmsnorm, attn_supported,
-                  causal_conv1d, l2_normalize, last_token_rmsnorm, linear_sk, mixer_proj, mixer_proj_ok, mlp,
-                  neg_exp_many, pack_key_mask, packed_attention, patch_im2col, qkv_proj, split_rows, split_rows_n,
-                  ss2d_conv_stack, ss2d_merge_ln_gate, ss2d_proj, ss2d_proj_ok, token_embed, weight_cast_scope,
-                  wleft_mm)
+                  causal_conv1d, l2_normalize, last_token_rmsnorm, linear_sk, mlp, neg_exp_many, pack_key_mask,
+                  packed_attention, patch_im2col, qkv_proj, split_rows, split_rows_n, ss2d_conv_stack,
+                  ss2d_merge_ln_gate, ss2d_proj, ss2d_proj_ok, token_embed, weight_cast_scope, wleft_mm)
 from .selective_scan_interface import (SS2D_REVERSE_GROUPS, SS2D_U_GROUPS, SelectiveScanFn, fine_state_scope,
                                        grouped_scan_fn, selective_scan_fn)
 
@@ -92,8 +91,6 @@ class MambaMixer(nn.Module):
         self.D._no_weight_decay = True
         self.out_proj = nn.Linear(self.d_inner, d_model, bias=False)
         self.du_handoff = True   # scan du -> x_proj's dX epilogue (ops.GradHandoff)
-        # x_proj + dt_proj as one HIP pass each way (ops.MixerProjFn); A/B toggle
-        self.fuse_proj = os.environ.get("MAMBA_CLIP_AMD_FUSE_MIXER_PROJ", "0") == "1"
 
     def forward(self, hidden, A=None):  # (B, L, d_model) contiguous; A: -exp(A_log) when the tower formed it
         Bsz, L, dm = hidden.shape
@@ -113,31 +110,21 @@ class MambaMixer(nn.Module):
         if A is None:
             A = -torch.exp(self.A_log.float())
         dz = (slab, di) if slab is not None else None
-        if self.fuse_proj and mixer_proj_ok(x_cm, R, N):
-            # x_proj and dt_proj in one pass over x (and one backward pass over ddelta that also adds
-            # the scan's du into dx: ops.GradHandoff)
-            hand = GradHandoff() if (self.du_handoff and x.requires_grad) else None
-            Brows, Crows, delta = mixer_proj(x_cm, self.x_proj.weight, self.dt_proj.weight, hand)
-            Bm = Brows.view(N, Bsz, L).transpose(0, 1)                         # (B, N, L)
-            Cm = Crows.view(N, Bsz, L).transpose(0, 1)
-            delta = delta.view(di, Bsz, L).transpose(0, 1)
-            y = mixer_scan(x, delta, A, Bm, Cm, self.D.float(), z, self.dt_proj.bias.float(), dz, hand)
-        else:
-            # x's gradient: the scan's du is handed to x_proj's backward, which adds its dX in the
-            # GEMM epilogue (ops.GradHandoff) instead of autograd summing the two producers
-            hand = GradHandoff() if (self.du_handoff and x.is_cuda and x.requires_grad) else None
-            x_dbl = wleft_mm(self.x_proj.weight, x_cm, hand)                   # (R+2N, B*L)
-            # dt_proj's backward writes d(dt_raw) and the scan's writes dB / dC straight into one
-            # (R+2N, B*L) gradient slab: no transpose copies of dB / dC, no concatenation
-            pslab = GradSlab(R + 2 * N, Bsz * L, x_dbl.dtype, x_dbl.device) if (x_dbl.requires_grad and
-                                                                                 XPROJ_GRAD_SLAB) else None
-            dt_raw, Bm, Cm = split_rows_n(x_dbl, (R, N, N), pslab)
-            delta = wleft_mm(self.dt_proj.weight, dt_raw, out_slab=(pslab, 0) if pslab is not None else None)
-            delta = delta.view(di, Bsz, L).transpose(0, 1)
-            Bm = Bm.view(N, Bsz, L).transpose(0, 1)                           # (B, N, L)
-            Cm = Cm.view(N, Bsz, L).transpose(0, 1)
-            y = mixer_scan(x, delta, A, Bm, Cm, self.D.float(), z, self.dt_proj.bias.float(), dz, hand,
-                           (pslab, R, R + N) if pslab is not None else None)
+        # x's gradient: the scan's du is handed to x_proj's backward, which adds its dX in the
+        # GEMM epilogue (ops.GradHandoff) instead of autograd summing the two producers
+        hand = GradHandoff() if (self.du_handoff and x.is_cuda and x.requires_grad) else None
+        x_dbl = wleft_mm(self.x_proj.weight, x_cm, hand)                   # (R+2N, B*L)
+        # dt_proj's backward writes d(dt_raw) and the scan's writes dB / dC straight into one
+        # (R+2N, B*L) gradient slab: no transpose copies of dB / dC, no concatenation
+        pslab = GradSlab(R + 2 * N, Bsz * L, x_dbl.dtype, x_dbl.device) if (x_dbl.requires_grad and
+                                                                             XPROJ_GRAD_SLAB) else None
+        dt_raw, Bm, Cm = split_rows_n(x_dbl, (R, N, N), pslab)
+        delta = wleft_mm(self.dt_proj.weight, dt_raw, out_slab=(pslab, 0) if pslab is not None else None)
+        delta = delta.view(di, Bsz, L).transpose(0, 1)
+        Bm = Bm.view(N, Bsz, L).transpose(0, 1)                           # (B, N, L)
+        Cm = Cm.view(N, Bsz, L).transpose(0, 1)
+        y = mixer_scan(x, delta, A, Bm, Cm, self.D.float(), z, self.dt_proj.bias.float(), dz, hand,
+                       (pslab, R, R + N) if pslab is not None else None)
         y2 = y.transpose(0, 1).reshape(di, Bsz * L)                            # view: y keeps x's layout
         out = linear_sk(y2.t(), self.out_proj.weight)                          # (B*L, d_model)
         return out.view(Bsz, L, dm)

@@ -891,6 +891,17 @@ def colsum(x):
     return out
 
 
+def _bias_grad(gy, g2):
+    """(C,) fp32 column sums of g2, the (R, C) rows of the output gradient gy: the sums gy's producer left
+    on it (COLSUM_ATTR; LayerNorm backward) while gy is unchanged since, else mc_colsum (torch on the CPU)."""
+    pre = getattr(gy, COLSUM_ATTR, None)
+    if pre is not None and pre[1] == gy._version and pre[0].shape[0] == g2.shape[1]:
+        return pre[0]
+    if g2.is_cuda:
+        return colsum(g2)
+    return torch.sum(g2, 0, dtype=torch.float32)
+
+
 class L2NormalizeFn(torch.autograd.Function):
     """torch.nn.functional.normalize(x, dim=-1) for 2-D x (the towers' output features, reference
     model.py:1011-1017): fp32 out; one wave per row each way (mc_l2norm_fwd / _bwd)."""
@@ -1263,13 +1274,7 @@ class LinearSK(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             dw = wgrad(g2.t(), x2)
         if ctx.has_bias and ctx.needs_input_grad[2]:
-            pre = getattr(gy, COLSUM_ATTR, None)   # column sums taken by the producer of gy (LayerNorm bwd)
-            if pre is not None and pre[1] == gy._version and pre[0].shape[0] == g2.shape[1]:
-                db = pre[0]
-            elif g2.is_cuda:
-                db = colsum(g2)
-            else:
-                db = torch.sum(g2, 0, dtype=torch.float32)
+            db = _bias_grad(gy, g2)
         return dx, dw, db
 
 
@@ -1300,31 +1305,6 @@ def gemm_small_k(wc, Xc):
     return y
 
 
-# w @ X with few output rows and a long reduction (the mixer's x_proj forward, 80 x 1536) on
-# mc_gemm_skinny_m.  A/B toggle, off: as built it streams X at 1.7 TB/s (38.3 vs the library's 25.7 us at
-# C2; step +0.1-0.25 ms, profiles/r05/mixer/) -- one 8 KB chunk in flight per wave, latency-bound.
-SKINNY_M_HIP = os.environ.get("MAMBA_CLIP_AMD_SKINNY_M_HIP", "0") == "1"
-
-
-def skinny_m_ok(wc, Xc):
-    M, K = wc.shape
-    return (SKINNY_M_HIP and Xc.is_cuda and wc.dtype == Xc.dtype and Xc.dtype in (torch.bfloat16, torch.float16)
-            and 0 < M <= 96 and K % 256 == 0 and Xc.shape[1] % 8 == 0 and Xc.stride(1) == 1
-            and Xc.stride(0) % 8 == 0 and Xc.data_ptr() % 16 == 0 and wc.stride(1) == 1 and wc.stride(0) % 4 == 0
-            and wc.data_ptr() % 8 == 0)
-
-
-def gemm_skinny_m(wc, Xc):
-    """wc (M, K) @ Xc (K, T) on mc_gemm_skinny_m (caller checks skinny_m_ok)."""
-    M, K = wc.shape
-    T = Xc.shape[1]
-    y = torch.empty(M, T, device=Xc.device, dtype=Xc.dtype)
-    _lib.check(_lib.load().mc_gemm_skinny_m(M, K, T, _lib.dtype_code(Xc.dtype), wc.data_ptr(), wc.stride(0),
-                                            Xc.data_ptr(), Xc.stride(0), y.data_ptr(), T,
-                                            _lib.stream_handle(Xc.device)), "mc_gemm_skinny_m")
-    return y
-
-
 class WeightLeftMM(torch.autograd.Function):
     """y = w @ X for a weight w (N, K) and activations X (K, M) (channel-major GEMMs of the Mamba mixer)."""
 
@@ -1335,8 +1315,6 @@ class WeightLeftMM(torch.autograd.Function):
         with torch.autocast("cuda", enabled=False):
             if small_k_ok(wc, Xc):
                 y = gemm_small_k(wc, Xc)
-            elif skinny_m_ok(wc, Xc):
-                y = gemm_skinny_m(wc, Xc)
             else:
                 y = torch.mm(wc, Xc)
         ctx.save_for_backward(wc, Xc)
@@ -1376,85 +1354,6 @@ class WeightLeftMM(torch.autograd.Function):
 
 def wleft_mm(weight, X, handoff=None, out_slab=None):
     return WeightLeftMM.apply(weight, X, handoff, out_slab)
-
-
-def mixer_proj_ok(x_cm, rank, dstate):
-    """Shapes mc_mixer_proj_* take: 16-bit (D, T) rows with unit token stride, D % 64, T % 8, rank % 16
-    in [16, 96], dstate 16 (every reference config)."""
-    dt = _compute_dtype(x_cm)
-    D, T = x_cm.shape
-    return (x_cm.is_cuda and dt in (torch.bfloat16, torch.float16) and x_cm.stride(1) == 1 and D % 64 == 0
-            and T % 8 == 0 and T > 0 and rank % 16 == 0 and 16 <= rank <= 96 and dstate == 16
-            and x_cm.stride(0) % 8 == 0 and x_cm.data_ptr() % 16 == 0)
-
-
-class MixerProjFn(torch.autograd.Function):
-    """x_dbl = x_proj(x), delta = dt_proj.weight @ x_dbl[:R] for the Mamba mixer's channel-major
-    activations (D, T), in one HIP pass (mc_mixer_proj_fwd); backward: d_x_dbl and dx = x_proj^T d_x_dbl
-    + du (the scan's gradient, handed over by ops.GradHandoff) in one pass (mc_mixer_proj_bwd), the two
-    weight gradients as split-K GEMMs (ops.wgrad).  Same roundings as the library-GEMM chain:
-    x_dbl, delta, d_dtraw and dx stored once in the activation dtype."""
-
-    @staticmethod
-    def forward(ctx, x, w_x, w_dt, handoff):
-        dt = _compute_dtype(x)
-        lib = _lib.load()
-        xc = x if x.dtype == dt else x.to(dt)
-        wx, wdt = _wcast(w_x, dt).contiguous(), _wcast(w_dt, dt).contiguous()
-        D, T = xc.shape
-        P, R = wx.shape[0], wdt.shape[1]
-        xd = torch.empty(P, T, device=xc.device, dtype=dt)
-        delta = torch.empty(D, T, device=xc.device, dtype=dt)
-        p = _lib.MixerProjParams()
-        p.dim, p.tokens, p.rank, p.proj_rows, p.dtype = D, T, R, P, _lib.dtype_code(dt)
-        p.x_ld, p.x_dbl_ld, p.delta_ld = xc.stride(0), T, T
-        p.x, p.w_x, p.w_dt, p.x_dbl, p.delta = xc.data_ptr(), wx.data_ptr(), wdt.data_ptr(), xd.data_ptr(), delta.data_ptr()
-        _lib.check(lib.mc_mixer_proj_fwd(ctypes.byref(p), _lib.stream_handle(xc.device)), "mc_mixer_proj_fwd")
-        ctx.save_for_backward(xc, wx, wdt, xd)
-        ctx.handoff = handoff
-        # B and C rows as their own outputs (views of x_dbl): their gradients arrive separately, so
-        # autograd never builds a zero-filled (P, T) gradient of x_dbl
-        return xd[R:P - 16], xd[P - 16:], delta
-
-    @staticmethod
-    def backward(ctx, g_b, g_c, g_delta):
-        xc, wx, wdt, xd = ctx.saved_tensors
-        lib = _lib.load()
-        D, T = xc.shape
-        P, R = wx.shape[0], wdt.shape[1]
-        dt = xc.dtype
-        if g_delta is None:
-            g_delta = torch.zeros(D, T, device=xc.device, dtype=dt)
-        g_delta = _hip_rows(g_delta.to(dt), 8, "MixerProjFn")
-        g_b = _hip_rows(g_b.to(dt), 8, "MixerProjFn") if g_b is not None else None
-        g_c = _hip_rows(g_c.to(dt), 8, "MixerProjFn") if g_c is not None else None
-        du = ctx.handoff.take() if ctx.handoff is not None else None
-        if du is not None:
-            du = du.transpose(0, 1)                          # (B, D, L) channel-major -> (D, B, L)
-            du = du.reshape(D, T) if du.is_contiguous() else du.reshape(D, T).contiguous()
-            du = du.to(dt)
-        dxd = torch.empty(P, T, device=xc.device, dtype=dt)
-        dx = torch.empty(D, T, device=xc.device, dtype=dt)
-        p = _lib.MixerProjBwdParams()
-        p.dim, p.tokens, p.rank, p.proj_rows, p.dtype = D, T, R, P, _lib.dtype_code(dt)
-        p.g_delta_ld, p.d_x_dbl_ld, p.dx_ld = g_delta.stride(0), T, T
-        p.g_delta, p.w_x, p.w_dt, p.d_x_dbl, p.dx = g_delta.data_ptr(), wx.data_ptr(), wdt.data_ptr(), dxd.data_ptr(), dx.data_ptr()
-        if g_b is not None:
-            p.g_b, p.g_b_ld = g_b.data_ptr(), g_b.stride(0)
-        if g_c is not None:
-            p.g_c, p.g_c_ld = g_c.data_ptr(), g_c.stride(0)
-        if du is not None:
-            p.du, p.du_ld = du.data_ptr(), du.stride(0)
-        _lib.check(lib.mc_mixer_proj_bwd(ctypes.byref(p), _lib.stream_handle(xc.device)), "mc_mixer_proj_bwd")
-        dw_x = wgrad(dxd, xc.t()) if ctx.needs_input_grad[1] else None
-        dw_dt = wgrad(g_delta, xd[:R].t()) if ctx.needs_input_grad[2] else None
-        return (dx if ctx.needs_input_grad[0] else None), dw_x, dw_dt, None
-
-
-def mixer_proj(x_cm, w_x, w_dt, handoff=None):
-    """(B rows (16, T), C rows (16, T), delta (D, T)) for the mixer's channel-major x (D, T): the
-    x_dbl = [dt_raw; B; C] split of x_proj with dt_raw consumed by dt_proj inside; see MixerProjFn."""
-    return MixerProjFn.apply(x_cm, w_x, w_dt, handoff)
 
 
 # ---------------------------------------------------------------------------- fused bias-gradient passes (mc_ops.h)
@@ -1592,11 +1491,7 @@ class MlpFn(torch.autograd.Function):
         g2 = gy.reshape(-1, gy.shape[-1]).to(h.dtype)
         if not _aligned_rows(g2, 8):
             g2 = g2.contiguous()
-        pre = getattr(gy, COLSUM_ATTR, None)   # gy's column sums taken by its producer (LayerNorm bwd)
-        if pre is not None and pre[1] == gy._version and pre[0].shape[0] == g2.shape[1]:
-            db2 = pre[0]
-        else:
-            db2 = colsum(g2)
+        db2 = _bias_grad(gy, g2)
         dw2 = wgrad(g2.t(), a)
         wt2 = (ctx.wt2 if ctx.wt2 is not None else w2c.t().contiguous()) if MLP_HIP_BWD else None
         if MLP_HIP_BWD and linear_hip_ok(g2, wt2) and _aligned_rows(h, 8):
@@ -1654,17 +1549,8 @@ class FC1GeluFn(torch.autograd.Function):
         cols = h.shape[-1]
         h2 = h.reshape(-1, cols)
         g2 = ga.reshape(-1, cols).to(h.dtype)
-        V = 16 // h.element_size()
         if h.is_cuda:
-            lib = _lib.load()
-            h2, g2 = _hip_rows(h2, V, "fc1_gelu backward"), _hip_rows(g2, V, "fc1_gelu backward")
-            gh = torch.empty_like(h2)
-            db = torch.empty(cols, device=h.device, dtype=torch.float32)
-            ws_b = lib.mc_grad_colsum_workspace_bytes(h2.shape[0], cols)
-            ws = _ws(ws_b, h.device)
-            _lib.check(lib.mc_gelu_bwd(h2.shape[0], cols, _lib.dtype_code(h.dtype), h2.data_ptr(), h2.stride(0),
-                                       g2.data_ptr(), g2.stride(0), gh.data_ptr(), gh.stride(0), db.data_ptr(),
-                                       ws.data_ptr(), ws_b, _lib.stream_handle(h.device)), "mc_gelu_bwd")
+            gh, db = _gelu_bwd(h2, g2)
         else:   # CPU tensors (the CPU restatement tests): the same math in torch
             gh = torch.ops.aten.gelu_backward(g2, h2)
             db = gh.sum(0, dtype=torch.float32)
