@@ -192,6 +192,66 @@ typedef struct mc_retrieval_params {
 int mc_retrieval_ranks(const mc_retrieval_params* p, void* stream);
 size_t mc_retrieval_ranks_workspace_bytes(int32_t M, int32_t N);
 
+/* Pairwise sigmoid loss (SigLIP; Zhai et al., "Sigmoid Loss for Language Image
+ * Pre-Training", Alg. 1) without the M x N logits in memory.  The reference's
+ * --siglip switch prepares init_logit_scale = log 10 and init_logit_bias = -10
+ * (pipeline.py:213-216) for the biased logits of ClipModel.get_logits
+ * (model.py:1047-1063) and stops there; this is the loss those logits feed.
+ * For X (M x K) and Y (N x K), K contiguous, both bf16 or both fp32:
+ *   z[i, j] = scale * sum_k X[i, k] Y[j, k] + bias                  (never stored)
+ *   y[i, j] = +1 if j == i + row_off else -1     (a row whose label column falls
+ *                                                 outside [0, N) has no positive)
+ *   loss    = coef * sum_{i < M, j < N} softplus(-y z)      (= -coef * sum log sigmoid(y z))
+ * scale = *scale_dev if scale_dev != NULL else scale, bias likewise: device
+ * scalars are read on the device (no host sync).  No row or column statistics
+ * and no global normalisation: a rank's term of the multi-GPU loss is this call
+ * on (local X) x (all Y) with row_off = b_local * rank.
+ * mc_sigmoid_loss_fwd: the 128 x 128 GEMM tiles of mc_gemm_nt (same K loop, same
+ * accumulator scaling as mc_ce_fused_fwd) reduce softplus(-y z), evaluated as
+ * max(t, 0) + log1p(exp(-|t|)), to one fp32 partial per tile; a fold kernel sums
+ * the partials in a fixed order into *loss_out (no atomics: repeated calls give
+ * identical bits).  Workspace: mc_sigmoid_loss_fwd_workspace_bytes, one float
+ * per tile rounded up to 16 B.
+ * mc_sigmoid_loss_grad: recomputes the tiles and writes, in g_dtype,
+ *   G[i, j] = gmul * gout * coef * (sigmoid(z) - [j == i + row_off])
+ * with gout = *gout_dev (NULL = 1) and gmul = scale if g_times_scale else 1 (so
+ * G @ Y is dX directly).  Called on a block of rows of X (or, with the roles
+ * swapped and row_off negated, of Y) it yields one block of dz (or dz^T) at a
+ * time.  If dscale_out / dbias_out are not NULL it also returns
+ *   *dscale_out = gout * coef * sum (sigmoid(z) - [label]) (z - bias) / scale
+ *   *dbias_out  = gout * coef * sum (sigmoid(z) - [label])
+ * through per-tile partials and the same fixed-order fold; the workspace
+ * (mc_sigmoid_loss_grad_workspace_bytes, two floats per tile, each array rounded
+ * up to 16 B) is needed only then.
+ * Errors: null params / X / Y / loss_out (fwd) / G (grad) MC_ERR_INVALID; a dtype
+ * other than bf16 / fp32 (fp8 included) MC_ERR_DTYPE; M, N or K <= 0,
+ * |row_off| >= 2^30 or ldg < N MC_ERR_SHAPE; a missing, short or unaligned
+ * workspace MC_ERR_WORKSPACE. */
+typedef struct mc_sigmoid_loss_params {
+  int32_t M, N, K;
+  int32_t in_dtype;
+  const void* X; int64_t ldx;
+  const void* Y; int64_t ldy;
+  float scale;                  /* used when scale_dev == NULL */
+  const float* scale_dev;
+  float bias;                   /* used when bias_dev == NULL */
+  const float* bias_dev;
+  int64_t row_off; float coef;
+  float* loss_out;              /* fwd: device scalar */
+  const float* gout_dev;        /* grad: upstream scalar, NULL = 1 */
+  int32_t g_dtype;              /* grad: fp32 or bf16 */
+  int32_t g_times_scale;
+  void* G; int64_t ldg;         /* grad: M x N block */
+  float* dscale_out;            /* grad: device scalar, nullable */
+  float* dbias_out;             /* grad: device scalar, nullable */
+  void* workspace; size_t workspace_bytes;
+} mc_sigmoid_loss_params;
+
+int mc_sigmoid_loss_fwd(const mc_sigmoid_loss_params* p, void* stream);
+size_t mc_sigmoid_loss_fwd_workspace_bytes(int32_t M, int32_t N);
+int mc_sigmoid_loss_grad(const mc_sigmoid_loss_params* p, void* stream);
+size_t mc_sigmoid_loss_grad_workspace_bytes(int32_t M, int32_t N);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,13 @@
 //    forward records each label's logit; a second sweep of the same tiles counts,
 //    per row and per column, the logits greater than / equal to it
 //    (rank_count_epilogue); rank_fold_kernel sums the tile counts.  No n x n buffer.
+//  * pairwise sigmoid loss (mc_sigmoid_loss_fwd / _grad): the SigLIP loss the reference's
+//    --siglip switch prepares logit_scale = log 10 and logit_bias = -10 for and then drops
+//    (pipeline.py:213-216), on the logits of ClipModel.get_logits (model.py:1047-1063):
+//    z = scale * X Y^T + bias, loss = coef * sum softplus(-y z) with y = +1 on the label diagonal
+//    and -1 elsewhere.  Forward: kEpi 4 reduces each tile to one partial, sum_partials_kernel
+//    folds them.  Gradient: kEpi 5 writes coef * (sigmoid(z) - [label]) through the GEMM's store
+//    epilogue and reduces the logit_scale / logit_bias gradients per tile.  No atomics.
 #include <algorithm>
 #include <cstdlib>
 
@@ -66,6 +73,10 @@ struct GemmArgs {
   float* tgt_r; float* tgt_c;               // kEpi 1: target logits (written by the tile holding them)
   float* gpart;                             // kEpi 2: per-workgroup sum(G * S), nullable
   uint32_t* rcnt; uint32_t* ccnt;           // kEpi 3: packed (greater | equal << 16) counts [tiles_n][M], [tiles_m][N]
+  // pairwise sigmoid loss (kEpi 4 = forward, 5 = gradient): z = logit + beta, label column i + off_r,
+  // weight coef_r.  kEpi 4 writes its tile sum to gpart; kEpi 5 sum(g * logit) to gpart and sum(g) to bpart.
+  float beta; const float* beta_dev;
+  float* bpart;                             // kEpi 5: per-workgroup sum(G), nullable with gpart
 };
 
 typedef uint8_t fp8_t;   // OCP e4m3fn bits
@@ -300,9 +311,54 @@ __device__ __forceinline__ void rank_count_epilogue(const GemmArgs& g, const f32
   }
 }
 
+// softplus(t) = log(1 + exp(t)) = max(t, 0) + log1p(exp(-|t|)).  At SigLIP's initial point every
+// negative pair has t ~ -10 and contributes ~4.5e-5: a log(1 + e) would round those digits away in
+// u = 1 + e.  log1p(e) is formed from the hardware log2 of u plus the rounding error of that sum:
+// with c = u - 1 and d = e - c (both exact), log1p(e) = log(u) + log(1 + d / u) = log(u) + d / u to
+// fp32 accuracy, and d / u = d (1 - c) up to d c^2 <= 2^-24 c^2.  Two transcendentals per logit
+// (exp, log2) where the library log1pf costs several times that in the tile epilogue.
+__device__ __forceinline__ float softplus_f(float t) {
+  const float e = __expf(-fabsf(t));
+  const float u = 1.f + e, c = u - 1.f, d = e - c;
+  const float log1p_e = fmaf(__builtin_amdgcn_logf(u), 0.693147180559945309f, fmaf(-d, c, d));
+  return fmaxf(t, 0.f) + log1p_e;
+}
+
+// Forward epilogue of the pairwise sigmoid loss: z = logit + beta, t = -y z with y = +1 on the
+// label diagonal (col - row == off_r, the integer compare of the CE gradient epilogue) and -1
+// elsewhere; out-of-range elements add 0.  The tile's sum of softplus(t) goes to gpart[workgroup]:
+// lane sums in a fixed order, a butterfly over the wave, the four waves through LDS.
+__device__ __forceinline__ void sigmoid_loss_epilogue(const GemmArgs& g, const f32x4 (&acc)[4][4],
+                                                      const float (&row_scale)[4][4], const float (&col_scale)[4],
+                                                      float alpha, float beta, int row_base, int col_base, char* lds) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int dbase = col_base - row_base;   // col - row of acc[0][0][0]
+  float sum = 0.f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float z = (acc[i][j][r] * row_scale[i][r]) * (alpha * col_scale[j]) + beta;
+        const int d = dbase + 16 * (j - i) - r;
+        const bool ok = (row_base + i * 16 + r < g.M) && (col_base + j * 16 < g.N);
+        const float sp = softplus_f(d == g.off_r ? -z : z);
+        sum += ok ? sp : 0.f;
+      }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) sum += __shfl_xor(sum, o);
+  float* red = reinterpret_cast<float*>(lds);
+  __syncthreads();                                         // main-loop LDS reads done
+  if (lane == 0) red[w] = sum;
+  __syncthreads();
+  if (tid == 0) g.gpart[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
 // kEpi 0: C = alpha * sa * sb * A B^T.  kEpi 1 / 2: the same tile feeds a fused
 // softmax cross-entropy epilogue instead (statistics / gradient, see below).
 // kEpi 3: the rank-count epilogue above; the K loop is the one kEpi 1 runs.
+// kEpi 4 / 5: the pairwise sigmoid loss (forward sum / gradient block), same K loop again.
 template <typename TIn, typename TOut, bool kAligned, int kEpi>
 __global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmArgs g) {
   constexpr int E = (int)sizeof(TIn);
@@ -379,7 +435,9 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmArgs g) {
     }
 
   // gradient epilogue inputs, also loaded before the K loop
-  float lr[4][4], lcol[4], gout = 1.f;
+  float lr[4][4], lcol[4], gout = 1.f, beta = 0.f;
+  if constexpr (kEpi == 4 || kEpi == 5) beta = g.beta_dev ? *g.beta_dev : g.beta;
+  if constexpr (kEpi == 5) gout = g.gout_dev ? *g.gout_dev : 1.f;
   if constexpr (kEpi == 2) {
     gout = g.gout_dev ? *g.gout_dev : 1.f;
 #pragma unroll
@@ -478,6 +536,10 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmArgs g) {
     rank_count_epilogue(g, acc, row_scale, col_scale, alpha, row_base, col_base, lds, tm, tn, m0, n0);
     return;
   }
+  if constexpr (kEpi == 4) {
+    sigmoid_loss_epilogue(g, acc, row_scale, col_scale, alpha, beta, row_base, col_base, lds);
+    return;
+  }
   if constexpr (kEpi == 0) {
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -485,6 +547,49 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmArgs g) {
       for (int j = 0; j < 4; ++j)
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[i][j][r] = (acc[i][j][r] * row_scale[i][r]) * (alpha * col_scale[j]);
+  } else if constexpr (kEpi == 5) {
+    // G = gmul * coef (sigmoid(z) - [label]), z = logit + beta.  With e = exp(-|z|) and s = 1 / (1 + e):
+    // sigmoid(|z|) = s and sigmoid(-|z|) = e s, so the label's sigmoid(z) - 1 = -sigmoid(-z) is formed
+    // without cancellation.  The tile also sums g * logit (logit_scale gradient before the division by
+    // scale: logit = z - beta) and g (logit_bias gradient).
+    const float gmul = g.g_times_alpha ? gout * alpha : gout;
+    const int dbase = col_base - row_base;
+    float dsum = 0.f, bsum = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float v = (acc[i][j][r] * row_scale[i][r]) * (alpha * col_scale[j]);
+          const float z = v + beta;
+          const int d = dbase + 16 * (j - i) - r;
+          const float e = __expf(-fabsf(z)), s = __builtin_amdgcn_rcpf(1.f + e), es = e * s;
+          const float sig = z >= 0.f ? s : es, nsig = z >= 0.f ? es : s;   // sigmoid(z), sigmoid(-z)
+          float gv = g.coef_r * (d == g.off_r ? -nsig : sig);
+          const bool ok = (row_base + i * 16 + r < g.M) && (col_base + j * 16 < g.N);
+          gv = ok ? gv : 0.f;
+          dsum = fmaf(gv, v, dsum);
+          bsum += gv;
+          acc[i][j][r] = gv * gmul;
+        }
+    if (g.gpart) {
+      __shared__ float sred[8];
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) {
+        dsum += __shfl_xor(dsum, o);
+        bsum += __shfl_xor(bsum, o);
+      }
+      if (lane == 0) {
+        sred[w] = dsum * gout;
+        sred[4 + w] = bsum * gout;
+      }
+      __syncthreads();
+      if (tid == 0) {
+        g.gpart[blockIdx.x] = (sred[0] + sred[1]) + (sred[2] + sred[3]);
+        g.bpart[blockIdx.x] = (sred[4] + sred[5]) + (sred[6] + sred[7]);
+      }
+    }
   } else {
     // G = gout * (coef_r (softmax_row - onehot) + coef_c (softmax_col - onehot)) from the
     // recomputed logits; the labels are diagonals of col - row, so one integer compare each.
@@ -1588,6 +1693,102 @@ extern "C" int mc_retrieval_ranks(const mc_retrieval_params* p, void* stream) {
   const int nf = (int)(((int64_t)p->M + p->N + 255) / 256);
   hipLaunchKernelGGL(rank_fold_kernel, dim3(nf), dim3(256), 0, s, p->M, p->N, g.tiles_m, g.tiles_n, w.rcnt, w.ccnt,
                      g.off_r, g.off_c, p->gt_r, p->eq_r, p->gt_c, p->eq_c);
+  const hipError_t e = hipGetLastError();
+  MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e));
+  return MC_OK;
+}
+
+// ------------------------------------------------------------------ pairwise sigmoid loss (SigLIP)
+namespace {
+inline size_t sigmoid_tiles(int M, int N) { return (size_t)((M + BM - 1) / BM) * ((N + BN - 1) / BN); }
+
+int sigmoid_common(const mc_sigmoid_loss_params* p, const char* who, GemmArgs& g, bool& aligned) {
+  MC_CHECK(p != nullptr, MC_ERR_INVALID, "%s: null params", who);
+  MC_CHECK(p->in_dtype == MC_DTYPE_BF16 || p->in_dtype == MC_DTYPE_F32, MC_ERR_DTYPE,
+           "%s: inputs must be bf16 or fp32", who);
+  MC_CHECK(p->K > 0, MC_ERR_SHAPE, "%s: bad shape", who);
+  const int rc = fill_operands(g, who, p->M, p->N, p->K, p->in_dtype, p->X, p->ldx, p->Y, p->ldy, aligned);
+  if (rc != MC_OK) return rc;
+  MC_CHECK(p->row_off > -(1 << 30) && p->row_off < (1 << 30), MC_ERR_SHAPE, "%s: label offset out of range", who);
+  g.alpha = p->scale; g.alpha_dev = p->scale_dev;
+  g.beta = p->bias; g.beta_dev = p->bias_dev;
+  g.off_r = (int)p->row_off;
+  g.coef_r = p->coef;
+  return MC_OK;
+}
+
+template <typename TOut, int kEpi>
+void launch_sigmoid(const GemmArgs& g, int in_dtype, bool aligned, hipStream_t s) {
+  const dim3 grid(g.tiles_m * g.tiles_n), block(256);
+  if (in_dtype == MC_DTYPE_BF16) {
+    if (aligned) hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, TOut, true, kEpi>), grid, block, 0, s, g);
+    else hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, TOut, false, kEpi>), grid, block, 0, s, g);
+  } else {
+    if (aligned) hipLaunchKernelGGL((gemm_nt_kernel<float, TOut, true, kEpi>), grid, block, 0, s, g);
+    else hipLaunchKernelGGL((gemm_nt_kernel<float, TOut, false, kEpi>), grid, block, 0, s, g);
+  }
+}
+}  // namespace
+
+extern "C" size_t mc_sigmoid_loss_fwd_workspace_bytes(int32_t M, int32_t N) {
+  if (M <= 0 || N <= 0) return 0;
+  return al16(sigmoid_tiles(M, N) * sizeof(float));
+}
+
+extern "C" int mc_sigmoid_loss_fwd(const mc_sigmoid_loss_params* p, void* stream) {
+  const char* who = "mc_sigmoid_loss_fwd";
+  GemmArgs g;
+  bool aligned;
+  const int rc = sigmoid_common(p, who, g, aligned);
+  if (rc != MC_OK) return rc;
+  MC_CHECK(p->loss_out, MC_ERR_INVALID, "%s: null loss_out", who);
+  const size_t need = mc_sigmoid_loss_fwd_workspace_bytes(p->M, p->N);
+  MC_CHECK(p->workspace && aligned16(p->workspace) && p->workspace_bytes >= need, MC_ERR_WORKSPACE,
+           "%s: workspace must be >= %zu bytes, 16-B aligned", who, need);
+  g.gpart = reinterpret_cast<float*>(p->workspace);
+  hipStream_t s = (hipStream_t)stream;
+  launch_sigmoid<float, 4>(g, p->in_dtype, aligned, s);
+  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, g.gpart, g.tiles_m * g.tiles_n, p->coef, nullptr,
+                     p->loss_out);
+  const hipError_t e = hipGetLastError();
+  MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e));
+  return MC_OK;
+}
+
+// two partials per tile: sum(g * logit) then sum(g), each block 16-B aligned
+extern "C" size_t mc_sigmoid_loss_grad_workspace_bytes(int32_t M, int32_t N) {
+  if (M <= 0 || N <= 0) return 0;
+  return 2 * al16(sigmoid_tiles(M, N) * sizeof(float));
+}
+
+extern "C" int mc_sigmoid_loss_grad(const mc_sigmoid_loss_params* p, void* stream) {
+  const char* who = "mc_sigmoid_loss_grad";
+  GemmArgs g;
+  bool aligned;
+  const int rc = sigmoid_common(p, who, g, aligned);
+  if (rc != MC_OK) return rc;
+  MC_CHECK(p->G, MC_ERR_INVALID, "%s: null G", who);
+  MC_CHECK(p->g_dtype == MC_DTYPE_F32 || p->g_dtype == MC_DTYPE_BF16, MC_ERR_DTYPE, "%s: G must be fp32 or bf16", who);
+  MC_CHECK(p->ldg >= p->N, MC_ERR_SHAPE, "%s: ldg < N", who);
+  const bool stats = p->dscale_out || p->dbias_out;
+  const size_t need = mc_sigmoid_loss_grad_workspace_bytes(p->M, p->N);
+  MC_CHECK(!stats || (p->workspace && aligned16(p->workspace) && p->workspace_bytes >= need), MC_ERR_WORKSPACE,
+           "%s: workspace must be >= %zu bytes, 16-B aligned", who, need);
+  g.gout_dev = p->gout_dev; g.g_times_alpha = p->g_times_scale != 0;
+  g.C = p->G; g.ldc = p->ldg;
+  g.c_vec = aligned16(p->G) && p->ldg % 4 == 0;
+  g.c_vec16 = g.c_vec && p->ldg % 8 == 0;
+  g.gpart = stats ? reinterpret_cast<float*>(p->workspace) : nullptr;
+  g.bpart = stats ? reinterpret_cast<float*>(reinterpret_cast<char*>(p->workspace) + need / 2) : nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  if (p->g_dtype == MC_DTYPE_F32) launch_sigmoid<float, 5>(g, p->in_dtype, aligned, s);
+  else launch_sigmoid<bf16_t, 5>(g, p->in_dtype, aligned, s);
+  const int tiles = g.tiles_m * g.tiles_n;
+  if (p->dscale_out)   // sum(g * logit) / scale
+    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, g.gpart, tiles,
+                       p->scale_dev ? 1.f : 1.f / p->scale, p->scale_dev, p->dscale_out);
+  if (p->dbias_out)
+    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, g.bpart, tiles, 1.f, nullptr, p->dbias_out);
   const hipError_t e = hipGetLastError();
   MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e));
   return MC_OK;

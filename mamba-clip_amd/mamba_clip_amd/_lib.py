@@ -123,6 +123,19 @@ class RetrievalParams(ctypes.Structure):
     ]
 
 
+class SigmoidLossParams(ctypes.Structure):
+    """Mirror of ``mc_sigmoid_loss_params`` (include/mc_contrastive.h)."""
+    _fields_ = [
+        ("M", c_i32), ("N", c_i32), ("K", c_i32), ("in_dtype", c_i32),
+        ("X", c_vp), ("ldx", c_i64), ("Y", c_vp), ("ldy", c_i64),
+        ("scale", ctypes.c_float), ("scale_dev", c_fp), ("bias", ctypes.c_float), ("bias_dev", c_fp),
+        ("row_off", c_i64), ("coef", ctypes.c_float),
+        ("loss_out", c_fp), ("gout_dev", c_fp),
+        ("g_dtype", c_i32), ("g_times_scale", c_i32), ("G", c_vp), ("ldg", c_i64),
+        ("dscale_out", c_fp), ("dbias_out", c_fp), ("workspace", c_vp), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
 class QkvPackParams(ctypes.Structure):
     """Mirror of ``mc_qkv_pack_params`` (include/mc_ops.h)."""
     _fields_ = [
@@ -284,6 +297,10 @@ SYMBOLS = {
     "mc_ce_fused_grad_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32]),
     "mc_retrieval_ranks": (ctypes.c_int, [ctypes.POINTER(RetrievalParams), c_vp]),
     "mc_retrieval_ranks_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32]),
+    "mc_sigmoid_loss_fwd": (ctypes.c_int, [ctypes.POINTER(SigmoidLossParams), c_vp]),
+    "mc_sigmoid_loss_fwd_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32]),
+    "mc_sigmoid_loss_grad": (ctypes.c_int, [ctypes.POINTER(SigmoidLossParams), c_vp]),
+    "mc_sigmoid_loss_grad_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32]),
     "mc_add_rmsnorm_fwd": (ctypes.c_int, [c_i32, c_i32, c_i32, c_vp, c_fp, c_fp, ctypes.c_float, c_vp, c_fp, c_fp,
                                           c_vp]),
     "mc_add_rmsnorm_bwd": (ctypes.c_int, [c_i32, c_i32, c_i32, c_vp, c_fp, c_fp, c_fp, c_fp, c_vp, c_fp, c_fp, c_vp,

@@ -61,6 +61,11 @@ def build_parser():
     p.add_argument("--grad-checkpointing", action="store_true")
     p.add_argument("--local-loss", action="store_true")
     p.add_argument("--gather-with-grad", action="store_true")
+    p.add_argument("--siglip", action="store_true",
+                   help="train with the pairwise sigmoid loss (SigLipLoss): the stage-1 model starts from "
+                        "logit_scale = log 10 and logit_bias = -10; --local-loss and --gather-with-grad are "
+                        "ignored (each rank always scores its images against all texts, gathered with "
+                        "gradients); with --stage 2 it only changes the frozen model's initialisation")
     p.add_argument("--accum-freq", type=int, default=1)
     p.add_argument("--dist-url", type=str, default="env://")
     p.add_argument("--dist-backend", type=str, default="nccl")
@@ -95,7 +100,10 @@ def _make_scheduler(optimizer, args, total_steps):
 def build_model(args, device):
     from ..model import ClipClassifier, init_model
     name = args.model_stage_1 or args.model
-    model, _, _, _ = init_model(name)
+    model_kwargs = {}
+    if getattr(args, "siglip", False):        # pipeline.py:213-216
+        model_kwargs = dict(init_logit_scale=math.log(10), init_logit_bias=-10)
+    model, _, _, _ = init_model(name, **model_kwargs)
     if args.stage == 1:
         if args.lock_image:
             model.lock_image_tower()
@@ -119,7 +127,7 @@ def main(argv=None):
 
     from .. import _lib
     from ..data import get_synthetic_data
-    from ..loss import ClipLoss, cross_entropy_loss
+    from ..loss import ClipLoss, SigLipLoss, cross_entropy_loss
     from ..train import create_optimizer, create_scaler, train_one_epoch, wrap_ddp
     from ..tuning import load_gemm_tuning
     from ..utils import init_device, is_master
@@ -135,7 +143,9 @@ def main(argv=None):
     model = wrap_ddp(model, args, device)
     optimizer = create_optimizer(model, args)
     scaler = create_scaler(args, device)
-    if args.stage == 1:
+    if args.stage == 1 and args.siglip:
+        loss = SigLipLoss(cache_labels=True, rank=args.rank, world_size=args.world_size)
+    elif args.stage == 1:
         loss = ClipLoss(local_loss=args.local_loss, gather_with_grad=args.gather_with_grad, cache_labels=True,
                         rank=args.rank, world_size=args.world_size)
     else:

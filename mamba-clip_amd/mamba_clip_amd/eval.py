@@ -113,9 +113,18 @@ def _unwrap(model):
     return model.module if hasattr(model, "module") else model
 
 
-def _batch_clip_loss(image_features, text_features, logit_scale):
+def _batch_clip_loss(image_features, text_features, logit_scale, logit_bias=None):
     """(CE(logits, arange) + CE(logits^T, arange)) / 2 of one batch; on the GPU through the fused
-    logits + CE kernel (ClipLoss at world size 1), so no b x b logits are formed."""
+    logits + CE kernel (ClipLoss at world size 1), so no b x b logits are formed.  A model that
+    carries a logit_bias trains on the pairwise sigmoid loss, and that is its validation loss
+    (SigLipLoss at world size 1, fused as well)."""
+    if logit_bias is not None:
+        if image_features.is_cuda:
+            from .loss import SigLipLoss
+            return SigLipLoss()(image_features, text_features, logit_scale, logit_bias, output_dict=False)
+        logits = logit_scale.float() * image_features.float() @ text_features.float().t() + logit_bias.float()
+        signs = 2 * torch.eye(logits.shape[0]) - 1
+        return -F.logsigmoid(signs * logits).sum() / logits.shape[0]
     if image_features.is_cuda:
         from .loss import ClipLoss
         return ClipLoss()(image_features, text_features, logit_scale, output_dict=False)
@@ -200,7 +209,8 @@ def evaluate(model, data, epoch, args, tb_writer=None, tokenizer=None):
                         logit_scale = model_out["logit_scale"].mean()
                         img_buf.append(image_features)
                         txt_buf.append(text_features)
-                        total_loss = _batch_clip_loss(image_features, text_features, logit_scale)
+                        total_loss = _batch_clip_loss(image_features, text_features, logit_scale,
+                                                      model_out.get("logit_bias"))
                     else:
                         logits = getattr(model_out, "logits", model_out)
                         total_loss = F.cross_entropy(logits.float(), targets)

@@ -14,16 +14,24 @@ step (image and text stacked), the logits come from the MFMA GEMM of
 libmamba_clip_amd.so with logit_scale read on the device, and both softmax
 cross-entropies (and their gradients, incl. d logit_scale) are fused kernels
 over the fp32 logits -- no host sync, no eager softmax.
+
+SigLipLoss is the pairwise sigmoid loss the reference's --siglip switch prepares the
+model for (logit_scale = log 10, logit_bias = -10: pipeline.py:213-216) and never
+builds; create_loss returns it when args.siglip is set.
 """
 import torch
 import torch.distributed as dist
 import torch.distributed.nn  # noqa: F401  (gather_with_grad; the reference forgets it: SURVEY Appendix A.4)
 import torch.nn.functional as F
 
-from .ops import gemm_nt, scaled_logits_ce
+from .ops import gemm_nt, scaled_logits_ce, sigmoid_logits_loss
 
 
 def create_loss(args):
+    if getattr(args, "siglip", False):
+        # --local-loss / --gather-with-grad do not apply: the sigmoid loss is always "local images x
+        # all texts" over an autograd-aware gather
+        return SigLipLoss(cache_labels=True, rank=args.rank, world_size=args.world_size)
     return ClipLoss(
         local_loss=args.local_loss,
         gather_with_grad=args.gather_with_grad,
@@ -135,4 +143,68 @@ class ClipLoss(torch.nn.Module):
         # get_ground_truth's arange; keep its cache state as the reference does
         local = self.world_size > 1 and self.local_loss
         self.get_ground_truth(image_features.device, image_features.shape[0] if local else all_i.shape[0])
+        return {"contrastive_loss": loss} if output_dict else loss
+
+
+class SigLipLoss(torch.nn.Module):
+    """Pairwise sigmoid loss (Zhai et al., "Sigmoid Loss for Language Image Pre-Training", Alg. 1;
+    open_clip's SigLipLoss):
+
+        loss = -1/n * sum_ij log sigmoid(y_ij * (logit_scale * I_i . T_j + logit_bias)),
+
+    y_ij = +1 for the pairs (i, i) and -1 otherwise, n the number of images.  ``logit_scale`` is the
+    already-exponentiated scale and ``logit_bias`` the model's bias, as ClipModel emits them.  The
+    logits are never stored (ops.sigmoid_logits_loss), forward or backward.
+
+    World size W > 1: the loss needs no normalisation across pairs, so each rank takes its own b
+    images against ALL texts -- the text features gathered with the autograd-aware all_gather -- with
+    the positives at column ``b * rank + i`` and the weight 1/b.  That covers every (image, text)
+    pair of the whole batch exactly once over the ranks, as open_clip's neighbour exchange of text
+    chunks does: the mean of the rank losses is the whole-batch loss 1/(W b) * sum_all, and after
+    DDP's gradient averaging (the gather's backward sums each text's gradient over the ranks) every
+    parameter receives the whole-batch gradient.
+    """
+
+    def __init__(self, cache_labels=False, rank=0, world_size=1):
+        super().__init__()
+        self.cache_labels = cache_labels
+        self.rank = rank
+        self.world_size = world_size
+        self.labels = {}
+
+    def _texts(self, text_features):
+        if self.world_size > 1:
+            return torch.cat(torch.distributed.nn.all_gather(text_features), dim=0)
+        return text_features
+
+    def _row_off(self, image_features):
+        return image_features.shape[0] * self.rank if self.world_size > 1 else 0
+
+    def get_ground_truth(self, device, dtype, num_rows, num_cols=None, row_off=0) -> torch.Tensor:
+        """The +1 / -1 target matrix (num_rows x num_cols), +1 where column == row + row_off."""
+        num_cols = num_rows if num_cols is None else num_cols
+        key = (device, dtype, num_rows, num_cols, row_off)
+        if key in self.labels:
+            return self.labels[key]
+        rows = torch.arange(num_rows, device=device)[:, None] + row_off
+        cols = torch.arange(num_cols, device=device)[None, :]
+        labels = torch.where(rows == cols, 1.0, -1.0).to(dtype)
+        if self.cache_labels:
+            self.labels = {key: labels}
+        return labels
+
+    def get_logits(self, image_features, text_features, logit_scale, logit_bias=None):
+        """Materialised logit_scale * I @ T_all^T + logit_bias (this rank's images x all texts), fp32."""
+        scale = logit_scale.reshape(()).float()
+        dt = image_features.dtype if image_features.dtype == torch.bfloat16 else torch.float32
+        logits = gemm_nt(image_features.to(dt), self._texts(text_features).to(dt), alpha_dev=scale)
+        if logit_bias is not None:
+            logits = logits + logit_bias
+        return logits
+
+    def forward(self, image_features, text_features, logit_scale, logit_bias, output_dict=True, target=None):
+        # `target` is accepted and ignored, like ClipLoss
+        b = image_features.shape[0]
+        loss = sigmoid_logits_loss(image_features, self._texts(text_features), logit_scale, logit_bias,
+                                   self._row_off(image_features), 1.0 / b)
         return {"contrastive_loss": loss} if output_dict else loss

@@ -1077,18 +1077,21 @@ MODEL_CONFIGS = {
 }
 
 
-def build_clip(name):
+def build_clip(name, **clip_kwargs):
+    """``clip_kwargs`` (init_logit_scale, init_logit_bias) go to ClipModel: SigLIP training starts from
+    log 10 and -10 (pipeline.py:213-216)."""
     cfg = MODEL_CONFIGS[name]
     visual = VisionTransformer(**cfg["vision"])
     if "hf_bert" in cfg:
         text = HFBertTextEncoder(**cfg["hf_bert"])
     else:
         text = BertTextEncoder(**cfg["bert"]) if "bert" in cfg else MambaTextEncoder(**cfg["text"])
-    return ClipModel(visual, text)
+    return ClipModel(visual, text, **clip_kwargs)
 
 
-def init_model(model, tokenizer=None, aug_cfg=None, is_clip=False, use_tokenizer=False):
+def init_model(model, tokenizer=None, aug_cfg=None, is_clip=False, use_tokenizer=False, **model_kwargs):
     """Returns (model, preprocess_train, preprocess_val, tokenizer) like model.py:1257-1289.
+    ``model_kwargs`` (init_logit_scale, init_logit_bias) reach the ClipModel a config name builds.
 
     "medmamba" -> VSSM(depths=[2,2,8,2], dims=[64,128,256,512], num_classes=2);
     a MODEL_CONFIGS name -> a random-init ClipModel (no hub access offline);
@@ -1099,7 +1102,7 @@ def init_model(model, tokenizer=None, aug_cfg=None, is_clip=False, use_tokenizer
     elif isinstance(model, str):
         if model not in MODEL_CONFIGS:
             raise ValueError(f"unknown model {model!r}: offline build knows {sorted(MODEL_CONFIGS)}")
-        model = build_clip(model)
+        model = build_clip(model, **model_kwargs)
     elif callable(model):
         model = model()
     if is_clip and not isinstance(model, ClipModel):

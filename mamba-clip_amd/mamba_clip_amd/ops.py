@@ -8,6 +8,8 @@
                           sum of row- and/or column-softmax cross-entropies --
                           the dense part of ClipLoss (loss.py:89-147) -- fused:
                           the logits never exist in memory (mc_ce_fused_*).
+``sigmoid_logits_loss``   autograd op: the pairwise sigmoid (SigLIP) loss of
+                          scale * X @ Y.T + bias, fused the same way (mc_sigmoid_loss_*).
 ``ce_stats`` / ``ce_grad`` the unfused statistics / gradient kernels over a
                           materialised S (kept for logits the caller needs anyway).
 ``retrieval_ranks(X, Y, scale)``  evaluation: per-row / per-column counts of logits that beat or
@@ -388,6 +390,145 @@ class ScaledLogitsCE(torch.autograd.Function):
 
 def scaled_logits_ce(X, Y, scale, row_off=0, coef_r=1.0, col_off=0, coef_c=0.0):
     return ScaledLogitsCE.apply(X, Y, scale, row_off, coef_r, col_off, coef_c)
+
+
+def _sigmoid_params(X, Y, sc, bs, row_off, coef):
+    """sc / bs: a 0-d fp32 device tensor (read on the device) or a python float."""
+    p = _lib.SigmoidLossParams()
+    p.M, p.K = X.shape
+    p.N = Y.shape[0]
+    p.in_dtype = _lib.dtype_code(X.dtype)
+    p.X, p.ldx, p.Y, p.ldy = X.data_ptr(), X.stride(0), Y.data_ptr(), Y.stride(0)
+    if torch.is_tensor(sc):
+        p.scale_dev = sc.data_ptr()
+    else:
+        p.scale = float(sc)
+    if torch.is_tensor(bs):
+        p.bias_dev = bs.data_ptr()
+    else:
+        p.bias = float(bs)
+    p.row_off, p.coef = int(row_off), float(coef)
+    return p
+
+
+def sigmoid_loss_fwd(X, Y, sc, bs, row_off=0, coef=1.0):
+    """coef * sum_ij softplus(-y_ij z_ij), z = sc * X @ Y^T + bs, y = +1 where j == i + row_off else -1,
+    tile-wise on the matrix cores without storing z (mc_sigmoid_loss_fwd).  A 0-d fp32 device scalar."""
+    lib = _lib.load()
+    M, N = X.shape[0], Y.shape[0]
+    loss = torch.empty((), device=X.device, dtype=torch.float32)
+    p = _sigmoid_params(X, Y, sc, bs, row_off, coef)
+    ws_b = lib.mc_sigmoid_loss_fwd_workspace_bytes(M, N)
+    ws = _ws(ws_b, X.device)
+    p.loss_out, p.workspace, p.workspace_bytes = loss.data_ptr(), ws.data_ptr(), ws_b
+    _lib.check(lib.mc_sigmoid_loss_fwd(p, _lib.stream_handle(X.device)), "mc_sigmoid_loss_fwd")
+    return loss
+
+
+def sigmoid_loss_grad(X, Y, sc, bs, row_off, coef, gout, g_dtype, want_stats=False):
+    """(sc * G, dscale, dbias): one block of gout * dloss/dz recomputed from the features
+    (mc_sigmoid_loss_grad); ``G @ Y`` is then dX directly.  dscale / dbias are None unless asked for."""
+    lib = _lib.load()
+    M, N = X.shape[0], Y.shape[0]
+    G = torch.empty(M, N, device=X.device, dtype=g_dtype)
+    p = _sigmoid_params(X, Y, sc, bs, row_off, coef)
+    p.gout_dev = gout.data_ptr()
+    p.g_dtype, p.g_times_scale, p.G, p.ldg = _lib.dtype_code(g_dtype), 1, G.data_ptr(), N
+    dscale = dbias = ws = None
+    if want_stats:
+        stats = torch.empty(2, device=X.device, dtype=torch.float32)
+        dscale, dbias = stats[0], stats[1]
+        ws_b = lib.mc_sigmoid_loss_grad_workspace_bytes(M, N)
+        ws = _ws(ws_b, X.device)
+        p.dscale_out, p.dbias_out = dscale.data_ptr(), dbias.data_ptr()
+        p.workspace, p.workspace_bytes = ws.data_ptr(), ws_b
+    _lib.check(lib.mc_sigmoid_loss_grad(p, _lib.stream_handle(X.device)), "mc_sigmoid_loss_grad")
+    return G, dscale, dbias
+
+
+class SigmoidLogitsLoss(torch.autograd.Function):
+    """loss = coef * sum_ij softplus(-y_ij z_ij),  z = scale * X @ Y^T + bias,  y_ij = +1 where
+    j == i + row_off and -1 elsewhere: the pairwise sigmoid (SigLIP) loss.
+
+    Neither pass stores z.  Forward: mc_sigmoid_loss_fwd (tiles reduced to one partial each).
+    Backward, as in ScaledLogitsCE: dX in row blocks -- G_blk (recomputed by mc_sigmoid_loss_grad,
+    already times scale) @ Y -- and dY in column blocks from the transposed problem (roles of X / Y
+    swapped, label offset negated) -- G^T_blk @ X.  Blocks hold at most CE_GRAD_BLOCK_ELEMS elements.
+    The scale and bias gradients are summed over the row blocks of the X pass only.
+    """
+
+    @staticmethod
+    def forward(ctx, X, Y, scale, bias, row_off, coef):
+        dt = X.dtype if X.dtype in (torch.bfloat16, torch.float32) else torch.float32
+        Xc = X.to(dt).contiguous()
+        Yc = Y.to(dt).contiguous()
+        s_t, b_t = torch.is_tensor(scale), torch.is_tensor(bias)
+        sc = scale.reshape(()).to(device=Xc.device, dtype=torch.float32).contiguous() if s_t else float(scale)
+        bs = bias.reshape(()).to(device=Xc.device, dtype=torch.float32).contiguous() if b_t else float(bias)
+        loss = sigmoid_loss_fwd(Xc, Yc, sc, bs, row_off, coef)
+        ctx.save_for_backward(Xc, Yc, *([sc] if s_t else []), *([bs] if b_t else []))
+        ctx.cfg = (row_off, coef, X.dtype, Y.dtype, None if s_t else sc, None if b_t else bs,
+                   (scale.dtype, scale.shape) if s_t else None, (bias.dtype, bias.shape) if b_t else None)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        row_off, coef, xdt, ydt, sc, bs, smeta, bmeta = ctx.cfg
+        saved = list(ctx.saved_tensors)
+        Xc, Yc = saved[0], saved[1]
+        rest = saved[2:]
+        if smeta is not None:
+            sc = rest.pop(0)
+        if bmeta is not None:
+            bs = rest.pop(0)
+        gout = gout.reshape(()).float().contiguous()
+        gdt = Xc.dtype  # G feeds the GEMMs in the operands' dtype
+        M, N = Xc.shape[0], Yc.shape[0]
+        want_ds = smeta is not None and ctx.needs_input_grad[2]
+        want_db = bmeta is not None and ctx.needs_input_grad[3]
+        want_stats = want_ds or want_db
+        dX = dY = dscale = dbias = None
+        # second operands of dX = G @ Y and dY = G^T @ X as (K-contiguous) row-major transposes
+        Yt = Yc.t().contiguous() if Yc.dtype == torch.float32 else Yc.t()
+        Xt = Xc.t().contiguous() if Xc.dtype == torch.float32 else Xc.t()
+        if ctx.needs_input_grad[0] or want_stats:
+            dX = torch.empty_like(Xc) if ctx.needs_input_grad[0] else None
+            R = _block_rows(N)
+            ds_parts, db_parts = [], []
+            for r0 in range(0, M, R):
+                r1 = min(M, r0 + R)
+                G, ds, db = sigmoid_loss_grad(Xc[r0:r1], Yc, sc, bs, row_off + r0, coef, gout, gdt, want_stats)
+                if dX is not None:
+                    _mm_nt(G, Yt, dX[r0:r1])
+                if want_stats:
+                    ds_parts.append(ds)
+                    db_parts.append(db)
+            if want_stats:
+                dscale = ds_parts[0] if len(ds_parts) == 1 else torch.stack(ds_parts).sum()
+                dbias = db_parts[0] if len(db_parts) == 1 else torch.stack(db_parts).sum()
+            dX = dX.to(xdt) if dX is not None else None
+        if ctx.needs_input_grad[1]:
+            dY = torch.empty_like(Yc)
+            R = _block_rows(M)
+            for c0 in range(0, N, R):
+                c1 = min(N, c0 + R)
+                # transposed problem: rows = columns c0..c1 of z, columns = rows of z; z's label
+                # j == i + row_off reads i == (j - c0) + (c0 - row_off) there
+                GT, _, _ = sigmoid_loss_grad(Yc[c0:c1], Xc, sc, bs, c0 - row_off, coef, gout, gdt)
+                _mm_nt(GT, Xt, dY[c0:c1])
+            dY = dY.to(ydt)
+        dS = dscale.to(smeta[0]).reshape(smeta[1]) if want_ds else None
+        dB = dbias.to(bmeta[0]).reshape(bmeta[1]) if want_db else None
+        return dX, dY, dS, dB, None, None
+
+
+def sigmoid_logits_loss(X, Y, scale, bias, row_off=0, coef=1.0):
+    """The pairwise sigmoid (SigLIP) loss of z = scale * X @ Y^T + bias (SigmoidLogitsLoss): X (M, K)
+    and Y (N, K) both bf16 or both fp32; ``scale`` / ``bias`` device scalar tensors (read on the
+    device, differentiable) or python floats; row i's positive is column i + row_off.  Asynchronous."""
+    if not -(1 << 30) < int(row_off) < (1 << 30):
+        raise ValueError("sigmoid_logits_loss: row_off must satisfy |row_off| < 2^30")
+    return SigmoidLogitsLoss.apply(X, Y, scale, bias, int(row_off), float(coef))
 
 
 # ---------------------------------------------------------------------------- encoder ops (include/mc_ops.h)
