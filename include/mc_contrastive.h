@@ -29,7 +29,8 @@ extern "C" {
 /* C[m, n] = alpha * sa[m] * sb[n] * sum_k A[m, k] * B[n, k]   (A: M x K, B: N x K, K contiguous)
  * dtype of A and B: MC_DTYPE_BF16 (MFMA bf16, fp32 accumulate),
  * MC_DTYPE_F32 (exact-fp32 MFMA) or MC_DTYPE_FP8_E4M3 (fp8 MFMA, fp32
- * accumulate; K, lda, ldb multiples of 16 and A, B 16-B aligned -- the
+ * accumulate to the instruction's ~2e-5 of sum |a b|; the fused CE entry points
+ * below sum fp8 operands exactly in fp32 on the bf16 MFMA; K, lda, ldb multiples of 16 and A, B 16-B aligned -- the
  * quantiser below pads K).  alpha = *alpha_dev if alpha_dev != NULL
  * (a device scalar such as logit_scale.exp(): no host sync), else alpha.
  * sa / sb: optional per-row dequantisation factors of A / B (fp32, M / N

@@ -14,7 +14,8 @@
 //    use the exact-fp32 v_mfma_f32_16x16x4_f32, fp8 (OCP e4m3fn) inputs
 //    v_mfma_f32_16x16x32_fp8_fp8 with a 64-element K slice (two MFMA k-steps
 //    per LDS fragment read) and per-row dequantisation factors applied in the
-//    epilogue.  alpha may live on the device (logit_scale.exp()), so the loss
+//    epilogue; the fused CE epilogues convert the fp8 fragments to bf16 in
+//    registers and run the bf16 MFMA instead (exact fp32 accumulation).  alpha may live on the device (logit_scale.exp()), so the loss
 //    needs no host sync.
 //  * quant_rows_fp8: one wave per row, amax -> 448/amax scale -> v_cvt_pk_fp8_f32.
 //  * ce_rows / ce_cols(+finalize): log-sum-exp statistics and per-label NLL
@@ -80,6 +81,21 @@ struct GemmArgs {
 };
 
 typedef uint8_t fp8_t;   // OCP e4m3fn bits
+
+// Eight e4m3 values (two dwords) as bf16: every e4m3 number is a bf16 number (3 mantissa bits, exponents
+// 2^-9 .. 2^8), so the conversion is the high half of v_cvt_pk_f32_fp8's exact fp32 result.
+__device__ __forceinline__ bf16x8 fp8x8_to_bf16(uint32_t lo, uint32_t hi) {
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  u32x4_t r;
+#pragma unroll
+  for (int w = 0; w < 2; ++w) {
+    const int src = (int)(w ? hi : lo);
+    const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8(src, false), b = __builtin_amdgcn_cvt_pk_f32_fp8(src, true);
+    r[2 * w] = (__float_as_uint(a[0]) >> 16) | (__float_as_uint(a[1]) & 0xffff0000u);
+    r[2 * w + 1] = (__float_as_uint(b[0]) >> 16) | (__float_as_uint(b[1]) & 0xffff0000u);
+  }
+  return __builtin_bit_cast(bf16x8, r);
+}
 
 __device__ __forceinline__ void lse_merge(float& m, float& s, float m2, float s2) {
   const float mm = fmaxf(m, m2);
@@ -491,17 +507,36 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmArgs g) {
         af[i] = *reinterpret_cast<const uint4*>(la + (wr * 64 + i * 16 + (lane & 15)) * kLdsStride + (lane >> 4) * 16);
         bf[i] = *reinterpret_cast<const uint4*>(lb + (wc * 64 + i * 16 + (lane & 15)) * kLdsStride + (lane >> 4) * 16);
       }
+      if constexpr (kEpi != 0) {
+        // The CE epilogues hold their logits to the fp32 lse tolerance (1e-5 absolute at |logit| ~ 20).
+        // v_mfma_f32_16x16x32_fp8_fp8 does not add real-valued products as an exact fp32 sum (measured:
+        // up to 2.5e-5 sum_k |a b|, 4e-4 on such a logit), so these instances feed the same bytes,
+        // converted exactly, to the bf16 MFMA of the same shape: exact products, fp32 accumulation.
 #pragma unroll
-      for (int h = 0; h < 2; ++h)
+        for (int h = 0; h < 2; ++h) {
+          bf16x8 b16[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const long a8 = h ? (long)(((uint64_t)af[i].w << 32) | af[i].z) : (long)(((uint64_t)af[i].y << 32) | af[i].x);
+          for (int j = 0; j < 4; ++j) b16[j] = h ? fp8x8_to_bf16(bf[j].z, bf[j].w) : fp8x8_to_bf16(bf[j].x, bf[j].y);
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const long b8 = h ? (long)(((uint64_t)bf[j].w << 32) | bf[j].z) : (long)(((uint64_t)bf[j].y << 32) | bf[j].x);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(a8, b8, acc[i][j], 0, 0, 0);
+          for (int i = 0; i < 4; ++i) {
+            const bf16x8 a16 = h ? fp8x8_to_bf16(af[i].z, af[i].w) : fp8x8_to_bf16(af[i].x, af[i].y);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a16, b16[j], acc[i][j], 0, 0, 0);
           }
         }
+      } else {
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const long a8 = h ? (long)(((uint64_t)af[i].w << 32) | af[i].z) : (long)(((uint64_t)af[i].y << 32) | af[i].x);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const long b8 = h ? (long)(((uint64_t)bf[j].w << 32) | bf[j].z) : (long)(((uint64_t)bf[j].y << 32) | bf[j].x);
+              acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(a8, b8, acc[i][j], 0, 0, 0);
+            }
+          }
+      }
     } else {
       // exact fp32: 4 MFMA K-steps of 4; lane holds A[row l&15][k = 4s + (l>>4)]
 #pragma unroll

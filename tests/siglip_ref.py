@@ -50,3 +50,23 @@ def sigmoid_logits_loss_full_ref(X, Y, scale, bias, row_off=0, coef=1.0):
         "abs_dbias": g.abs().sum(),
         "positives": int(lab.sum()),
     }
+
+
+def grad_block_ref(X, Y, scale, bias, row_off, coef, gout, bf16_out):
+    """(G, bound) of one mc_sigmoid_loss_grad block, G = gout * scale * coef * (sigmoid(z) - [label]), per
+    element in fp64.  The kernel forms q = sigmoid(z) off the label and sigmoid(-z) on it without
+    cancellation (e = exp(-|z|), 1 / (1 + e), e / (1 + e)), so its error is relative to q:
+        |dG| <= |gout scale coef| q ((1 - q) dz + (8 + |z|) 2^-23) + half_ulp_bf16(G) [bf16 G] + 1e-30
+    dz = eps_ij + 2^-23 (|z| + |bias|): the logit's accumulation bound (contrastive_ref.logits) and the
+    roundings of scale * acc and + bias, through dq/dz = q (1 - q); (8 + |z|) 2^-23 is twice the fast
+    exp ((2 + |z|) 2^-24), the reciprocal (1 ulp), 1 + e, e s, and the three products coef, gout, scale."""
+    from contrastive_ref import TINY, half_ulp_bf16, logits
+    S, eps = logits(X, Y, scale)
+    z = S + bias
+    lab = label_mask(X.shape[0], Y.shape[0], row_off)
+    sig = torch.sigmoid(z)
+    q = torch.where(lab, torch.sigmoid(-z), sig)
+    G = gout * scale * coef * torch.where(lab, -q, q)
+    dz = eps + 2.0 ** -23 * (z.abs() + abs(bias))
+    bound = abs(gout * scale * coef) * q * ((1 - q) * dz + (8 + z.abs()) * 2.0 ** -23)
+    return G, bound + (half_ulp_bf16(G) if bf16_out else 0.0) + TINY

@@ -62,11 +62,12 @@ def test_fp8_gemm_exact_integers_asymmetric():
 
 
 @pytest.mark.parametrize("M,N,K", [(256, 64, 64), (300, 200, 512), (1000, 520, 448), (64, 72, 128), (513, 1032, 320),
-                                   (2048, 4096, 512)])
+                                   (2048, 4096, 512), (130, 72, 192), (261, 136, 256), (70, 200, 384)])
 def test_fp8_panel_kernel_exact_integers(M, N, K):
     """The register-panel fp8 kernel (K % 64, K <= 512, N % 8): exact on small integers in fp32 and bf16 output
     (|sums| <= 256 for bf16), ragged panels / n-ranges / K steps, row and column factors and a device alpha
-    applied exactly (powers of two); the kernel asserted to be the panel kernel."""
+    applied exactly (powers of two); the kernel asserted to be the panel kernel.  Every NKS = K / 64
+    instance runs: 1, 2, 3 (130 x 72), 4 (261 x 136: a second, 5-row panel), 5, 6 (70 x 200), 7, 8."""
     from mamba_clip_amd import _lib, ops
     g = torch.Generator().manual_seed(M + N + K)
     A = torch.randint(-8, 9, (M, K), generator=g).float()
@@ -91,6 +92,37 @@ def test_fp8_panel_kernel_exact_integers(M, N, K):
         assert torch.equal(Cb.double(), A3.double() @ B3.double().T), (M, N, K)
     finally:
         ops.GEMM_NT_RECORD = None
+
+
+@pytest.mark.parametrize("M,N,K", [(200, 130, 640), (64, 64, 640)])
+def test_fp8_tile_kernel_exact_integers(M, N, K):
+    """sim_fp8_kernel (K % 128 == 0, not panel-eligible: K > 512), fp32 and bf16 output: exact on small
+    integers (|sums| <= 256 for bf16: products from {-1, 0, 1}, 256 columns of A live), ragged
+    tiles, row and column factors and a device alpha applied exactly; the kernel asserted through
+    GEMM_NT_RECORD.  N = 130 stores element-wise (ldc % 4 != 0), 64 x 64 is one live wave quadrant."""
+    from mamba_clip_amd import _lib, ops
+    g = torch.Generator().manual_seed(M + N + K)
+    A = torch.randint(-8, 9, (M, K), generator=g).float()
+    B = torch.randint(-8, 9, (N, K), generator=g).float()
+    B[:, 0] = torch.arange(N) % 9            # asymmetric
+    sa = 2.0 ** torch.randint(-3, 4, (M,), generator=g).float()
+    sb = 2.0 ** torch.randint(-3, 4, (N,), generator=g).float()
+    ref = 0.5 * sa[:, None].double() * sb[None, :].double() * (A.double() @ B.double().T)
+    A3 = torch.randint(-1, 2, (M, K), generator=g).float()
+    B3 = torch.randint(-1, 2, (N, K), generator=g).float()
+    A3[:, torch.arange(K) % 5 >= 2] = 0       # 256 live products, spread over all five K steps
+    ref3 = 2.0 * sa[:, None].double() * (A3.double() @ B3.double().T)
+    assert int((A3 != 0).any(0).sum()) <= 256 and bool((A3[:, 512:] != 0).any())
+    f8 = lambda t: t.to(torch.float8_e4m3fn).to(DEV)  # noqa: E731
+    ops.GEMM_NT_RECORD = []
+    try:
+        C = ops.gemm_nt(f8(A), f8(B), alpha_dev=torch.tensor(0.5, device=DEV), scale_a=sa.to(DEV), scale_b=sb.to(DEV))
+        Cb = ops.gemm_nt(f8(A3), f8(B3), alpha=2.0, out_dtype=torch.bfloat16, scale_a=sa.to(DEV))
+        assert ops.GEMM_NT_RECORD == [_lib.MC_GEMM_KERNEL_FP8_TILE] * 2
+    finally:
+        ops.GEMM_NT_RECORD = None
+    assert C.dtype == torch.float32 and torch.equal(C.cpu().double(), ref), (M, N, K)
+    assert Cb.dtype == torch.bfloat16 and torch.equal(Cb.cpu().double(), ref3), (M, N, K)
 
 
 def test_fp8_kernel_selection():

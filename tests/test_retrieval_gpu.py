@@ -47,7 +47,9 @@ def _int_features(M, N, K, seed, dtype):
 EXACT_CASES = [
     (5, 7, 8, 0, 0),
     (64, 64, 32, 0, 0),          # one wave quadrant live
-    (130, 130, 40, 0, 0),        # tile remainders both ways, K no multiple of the slice, unaligned rows
+    (130, 130, 40, 0, 0),        # tile remainders both ways, K no multiple of the slice; rows of 80 B (bf16) /
+                                 # 160 B (fp32) are 16-B multiples: the kAligned = true instances
+    (130, 130, 38, 0, 0),        # rows of 76 B / 152 B: the kAligned = false instances of kEpi 1 / 3, K % V != 0
     (257, 200, 64, 0, 0),        # 3 x 2 tiles
     (384, 384, 64, 0, 0),        # full tiles only, aligned path
     (100, 300, 32, 128, -128),   # labels in a later tile (local_loss); columns 0..127 have no label row
@@ -82,6 +84,20 @@ def test_retrieval_ranks_exact_on_integer_features(M, N, K, row_off, col_off, dt
         assert torch.equal(getattr(rs, name), got), f"{name} with a device scale"
     for a, b in zip(r, r2):
         assert torch.equal(a, b)                              # no atomics: repeated calls give the same bits
+    if K == 38:
+        # the same operands as views with a misaligned base and an aligned row stride (buf[:, 1:39] of 48
+        # columns: 96-B / 192-B rows starting 2 B / 4 B in): kAligned = false by the base-pointer route,
+        # NaN in the columns around the view
+        assert Xd.data_ptr() % 16 == 0 and (Xd.stride(0) * Xd.element_size()) % 16 != 0
+        views = []
+        for t in (Xd, Yd):
+            buf = torch.full((t.shape[0], 48), float("nan"), dtype=dtype, device=DEV)
+            buf[:, 1:39] = t
+            v = buf[:, 1:39]
+            assert v.data_ptr() % 16 != 0 and (v.stride(0) * v.element_size()) % 16 == 0
+            views.append(v)
+        for a, b in zip(r, retrieval_ranks(views[0], views[1], scale, row_off, col_off)):
+            assert torch.equal(a, b)
     torch.testing.assert_close(r.lse_r.cpu().double(), lse_r, rtol=1e-6, atol=1e-5)
     torch.testing.assert_close(r.lse_c.cpu().double(), lse_c, rtol=1e-6, atol=1e-5)
     if bool(ok_r.all()) and bool(ok_c.all()):

@@ -15,7 +15,7 @@ from types import SimpleNamespace
 import pytest
 import torch
 
-from siglip_ref import sigmoid_logits_loss_full_ref
+from siglip_ref import grad_block_ref, sigmoid_logits_loss_full_ref
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -23,7 +23,9 @@ DEV = "cuda"
 SHAPES = [
     (5, 7, 8, 0),            # small rectangular
     (64, 64, 32, 0),         # one wave quadrant
-    (130, 130, 40, 0),       # tile remainders both ways, K not a multiple of the slice, unaligned rows
+    (130, 130, 40, 0),       # tile remainders both ways, K not a multiple of the slice; rows of 80 B (bf16) /
+                             # 160 B (fp32) are 16-B multiples: the kAligned = true instances
+    (130, 130, 38, 0),       # rows of 76 B / 152 B: the kAligned = false instances of kEpi 4 / 5, K % V != 0
     (257, 200, 64, 0),       # 3 x 2 tiles
     (384, 384, 64, 0),       # full tiles, vector path
     (100, 300, 32, 128),     # a rank's positives in a later tile column
@@ -92,6 +94,34 @@ def test_sigmoid_logits_loss_matches_fp64(M, N, K, row_off, dtype, scale, bias):
     else:
         assert ref["positives"] >= 1
     _check(_run(X, Y, scale, bias, row_off, 1.0 / M), ref, dtype, (M, N, K, row_off, dtype, scale, bias))
+
+
+@pytest.mark.parametrize("M,N,K,aligned", [(130, 130, 38, False), (128, 128, 64, True)])
+def test_sigmoid_loss_grad_every_dtype_pair_per_element(M, N, K, aligned):
+    """mc_sigmoid_loss_grad called directly for one block: all four <TIn, TOut> pairs of the kEpi 5
+    instances (the autograd op only ever asks for G in the operands' dtype), kAligned false (76-B /
+    152-B rows, ragged tiles) and true (one full tile: vector stores), every element of G against fp64
+    within siglip_ref.grad_block_ref's bound; G bitwise equal with and without the scale / bias sums."""
+    from mamba_clip_amd import ops
+    scale, bias, coef = 10.0, -10.0, 1.0 / M
+    gout = torch.tensor(-0.37, device=DEV)
+    gout64 = float(gout.cpu().double())
+    sd, bd = torch.tensor(scale, device=DEV), torch.tensor(bias, device=DEV)
+    for in_dt in (torch.bfloat16, torch.float32):
+        X, Y = _features(M, N, K, 0, in_dt, seed=M * 7 + N * 3 + K)
+        Xd, Yd = X.to(DEV), Y.to(DEV)
+        assert (Xd.data_ptr() % 16 == 0 and (Xd.stride(0) * Xd.element_size()) % 16 == 0) == aligned
+        for g_dt in (torch.bfloat16, torch.float32):
+            ref, bound = grad_block_ref(X, Y, scale, bias, 0, coef, gout64, g_dt == torch.bfloat16)
+            G0, _, _ = ops.sigmoid_loss_grad(Xd, Yd, sd, bd, 0, coef, gout, g_dt)
+            G1, ds, db = ops.sigmoid_loss_grad(Xd, Yd, sd, bd, 0, coef, gout, g_dt, want_stats=True)
+            assert G0.dtype == g_dt and torch.equal(G0, G1)
+            assert bool(torch.isfinite(ds)) and bool(torch.isfinite(db))
+            got = G0.double().cpu()
+            assert bool(torch.isfinite(got).all())
+            ratio = float(((got - ref).abs() / bound).max())
+            print((M, N, K), in_dt, g_dt, f"G err / bound {ratio:.3f}")
+            assert ratio <= 1.0, (in_dt, g_dt, ratio)
 
 
 @pytest.mark.parametrize("M,N,K,row_off,dtype", [(300, 1100, 96, 400, torch.float32),
