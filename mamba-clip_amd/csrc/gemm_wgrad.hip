@@ -3,7 +3,7 @@
 //   C[m][n] = sum_t A(t, m) B(t, n)      (M, N <= a few thousand; T = batch * tokens, tens of thousands)
 //
 // This is dW = G^T X of every Linear in the image / text towers' backward (reference: the towers behind
-// encode_image / encode_text, /root/reference/src/mamba_clip/model.py:1011-1017; built at model.py:1270):
+// encode_image / encode_text, the reference's model.py:1011-1017; built at model.py:1270):
 // G is the output gradient, X the saved input, T the token count (C2 ViT: 50,432).  The output is
 // small (<= 9 tiles of 256 x 256 for the 768-wide layers) and the reduction long, so the launch
 // splits T over S workgroups per output tile (S ~ 256 CUs / tiles), writes one fp32 partial tile per
@@ -11,12 +11,12 @@
 //
 // Operand layouts (per operand, template flags):
 //  * token-major (TM): row t holds the features, A(t, m) = A[t * lda + m] -- a Linear's (tokens,
-//    features) activations / gradients.  The LDS tile is [64 t][256 features] (512-B rows, as the
-//    rows arrive from HBM) and MFMA fragments are read TRANSPOSED with ds_read_b64_tr_b16 (each lane
-//    gets 4 consecutive t of one feature; two reads make the 8 of a 16x16x32 operand);
+//    features) activations / gradients.  A half-tile's LDS image is [64 t][128 features] (256-B rows)
+//    and MFMA fragments are read TRANSPOSED with ds_read_b64_tr_b16 (each lane gets 4 consecutive t
+//    of one feature; two reads make the 8 of a 16x16x32 operand);
 //  * feature-major (FM): row m holds the tokens, A(t, m) = A[m * lda + t] -- the Mamba mixer's
-//    channel-major activations.  The LDS tile is [256 features][64 t] (128-B rows) and fragments
-//    are plain ds_read_b128 row reads.
+//    channel-major activations.  A half-tile's LDS image is [128 features][64 t] (128-B rows) and
+//    fragments are plain ds_read_b128 row reads.
 // Both land in LDS by global_load_lds_dwordx4 (16 B per lane, no VGPR round trip); the image is
 // lane-linear, so the bank swizzle sits on the SOURCE address and the matching read:
 //  * TM: 16-B chunk c of row r lives at slot c ^ 2 s(r), s(r) = (r & 3) | ((r >> 3) & 1) << 2 --
@@ -25,8 +25,14 @@
 //  * FM: chunk c of row r at slot c ^ ((r >> 1) & 7) (16 consecutive rows reading one chunk hit 16
 //    distinct 16-B bank slots; as sim_fp8_kernel).
 // Tile 256 x 256 x 64, 8 waves as 2 (m) x 4 (n), 128 x 64 per wave on v_mfma_f32_16x16x32_{bf16,f16}
-// (32 accumulators); two LDS stages of 64 KB, the next step's loads in flight across the step's
-// MFMAs (counted vmcnt, raw s_barrier), one workgroup per CU.
+// (32 accumulators); one loop, wgrad4p_kernel: four phases per K step over half-tile images, the two
+// wave rows one barrier apart (kStagger), 128 KB of LDS (two stages of four 16-KB half-tiles), the
+// next steps' loads in flight across the MFMAs (counted vmcnt, raw s_barrier), one workgroup per CU.
+//
+// The same loop with a 16-bit epilogue is mc_linear (Y = X W^T, optionally + bias or * gelu'(H)); the
+// short-K mc_gemm_small_k at the end of the file is a separate kernel.  The two-barrier loop this one
+// replaced and the fc1 + GELU epilogue were measured and removed; the rows-in-step
+// schedule (kStagger = false) survives for mc_gemm_wgrad behind MC_WGRAD_PIPE=4, with its tests.
 #include <type_traits>
 
 #include "mc_common.h"
@@ -40,8 +46,6 @@ namespace wgrad {
 
 constexpr int kBM = 256, kBN = 256, kBK = 64;
 constexpr int kThreads = 512;
-constexpr int kTileBytes = kBM * kBK * 2;       // one operand tile (32 KB)
-constexpr int kStage = 2 * kTileBytes;          // A + B (64 KB)
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
@@ -59,8 +63,7 @@ struct Args {
   // 16-bit epilogues (kEpi != kEpiSlab, mc_linear): the tile is stored TRANSPOSED, Y[n][m] -- n the
   // token (Y's row), m the feature (Y's column)
   void* Y; int64_t ldy;
-  void* Y2; int64_t ldy2;    // kEpiBiasGelu: gelu(h)
-  const void* bias;          // kEpiBias / kEpiBiasGelu: per feature m, operand dtype
+  const void* bias;          // kEpiBias: per feature m, operand dtype
   const void* H; int64_t ldh;   // kEpiGeluGrad: pre-activation at Y's positions
   float* colpart;            // kEpiGeluGrad: column sums of Y per token tile, [tiles_n][M] (or null)
 };
@@ -69,8 +72,7 @@ struct Args {
 constexpr int kEpiSlab = 0;       // fp32 C (or split-K slab), row m / column n
 constexpr int kEpiStore = 1;      // Y = C^T, 16-bit
 constexpr int kEpiBias = 2;       // Y = C^T + bias
-constexpr int kEpiBiasGelu = 3;   // Y = h = C^T + bias, Y2 = gelu(h)
-constexpr int kEpiGeluGrad = 4;   // Y = round(C^T) * gelu'(H), column sums of Y
+constexpr int kEpiGeluGrad = 3;   // Y = round(C^T) * gelu'(H), column sums of Y
 
 // One global_load_lds_dwordx4: 16 B per lane from gsrc to LDS byte address m0v + 16 * lane (m0v
 // wave-uniform).  asm, so hipcc's waitcnt pass does not drain it at the next LDS read; the loop
@@ -97,163 +99,10 @@ __device__ __forceinline__ s16x8 cat8(s16x4 lo, s16x4 hi) {
 __device__ __forceinline__ int tm_slot(int r, int c) { return c ^ (2 * ((r & 3) | (((r >> 3) & 1) << 2))); }
 __device__ __forceinline__ int fm_slot(int r, int c) { return c ^ ((r >> 1) & 7); }
 
-// glds source pointers of one operand tile for this lane (kInstr = 4 per wave): TM rows of 512 B (two
-// rows per instruction), FM rows of 128 B (eight rows per instruction).  Features past `dim` are
-// clamped (their results are never stored); the token range is always in bounds (T % 64 == 0).
-template <bool kFM>
-__device__ __forceinline__ void tile_sources(const char* base, int64_t ld, int dim, int f0, int w, int lane,
-                                             const char* (&src)[4], int64_t& step_bytes) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int pos = w * 4096 + j * 1024 + lane * 16;   // byte in the tile image
-    if constexpr (!kFM) {
-      const int r = pos >> 9, slot = (pos >> 4) & 31;   // row = token, 32 chunks of 8 features
-      const int c = tm_slot(r, slot);                   // involution: slot <-> chunk
-      const int f = min(f0 + 8 * c, dim - 8);
-      src[j] = base + ((int64_t)r * ld + f) * 2;
-    } else {
-      const int r = pos >> 7, slot = (pos >> 4) & 7;    // row = feature, 8 chunks of 8 tokens
-      const int c = fm_slot(r, slot);
-      const int f = min(f0 + r, dim - 1);
-      src[j] = base + ((int64_t)f * ld + 8 * c) * 2;
-    }
-  }
-  step_bytes = kFM ? (int64_t)kBK * 2 : (int64_t)kBK * ld * 2;
-}
-
-template <typename T, bool kAFM, bool kBFM>
-__global__ __launch_bounds__(kThreads, 1) void wgrad_kernel(const Args g) {
-  __shared__ __attribute__((aligned(16))) char lds[2 * kStage];   // the only LDS object
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = w >> 2, wc = w & 3;
-  // XCD-aware order: consecutive linear ids (same split, neighbouring tiles) share an XCD's L2
-  const int tiles = g.tiles_m * g.tiles_n;
-  const int nwg = tiles * g.splits;
-  const int bid0 = blockIdx.x, xcd = bid0 & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int lin = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid0 >> 3);
-  const int split = lin / tiles, tile = lin % tiles;
-  const int tm = tile % g.tiles_m, tn = tile / g.tiles_m;
-  const int m0 = tm * kBM, n0 = tn * kBN;
-  const int k_begin = (int)(((int64_t)split * g.nk) / g.splits), k_end = (int)(((int64_t)(split + 1) * g.nk) / g.splits);
-  const int nk = k_end - k_begin;
-
-  const char* srcA[4];
-  const char* srcB[4];
-  int64_t stepA, stepB;
-  tile_sources<kAFM>(g.A, g.lda, g.M, m0, w, lane, srcA, stepA);
-  tile_sources<kBFM>(g.B, g.ldb, g.N, n0, w, lane, srcB, stepB);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    srcA[j] += stepA * k_begin;
-    srcB[j] += stepB * k_begin;
-  }
-  const uint32_t lds_w = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_char*)(lds) + 4096u * w);
-  auto issue = [&](int step) __attribute__((always_inline)) {   // K step `step` (local) into stage step & 1
-    const uint32_t la = lds_w + (uint32_t)(step & 1) * kStage, lb = la + kTileBytes;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      glds16(srcA[j] + stepA * step, la + j * 1024);
-      glds16(srcB[j] + stepB * step, lb + j * 1024);
-    }
-  };
-
-  // ---- fragment read offsets (bytes within a stage's operand image)
-  // TM (transposed reads): lane l = 16 g + 4 q + p supplies row 8 g + 4 h + q (+ 32 kk), features
-  // [base + 4 p, +4): chunk base / 8 + (p >> 1), half 8 (p & 1).  s(r) = q | (g & 1) << 2 for every
-  // kk / h, so the slot XOR is a per-lane constant.
-  // FM (row reads): lane row (l & 15) of a 16-row tile, tokens [8 (l >> 4), +8) (+ 32 kk): chunk
-  // (l >> 4) + 4 kk.
-  const int fg = lane >> 4, fi = lane & 15, fq = fi >> 2, fp = fi & 3;
-  int offA[8], offB[4];
-#pragma unroll
-  for (int mi = 0; mi < 8; ++mi) {
-    const int base = wr * 128 + mi * 16;
-    if constexpr (!kAFM) {
-      const int r = 8 * fg + fq;
-      offA[mi] = r * 512 + (tm_slot(r, base / 8 + (fp >> 1)) << 4) + 8 * (fp & 1);
-    } else {
-      const int r = base + fi;
-      offA[mi] = r * 128;   // + slot (depends on kk) at the read
-    }
-  }
-#pragma unroll
-  for (int ni = 0; ni < 4; ++ni) {
-    const int base = wc * 64 + ni * 16;
-    if constexpr (!kBFM) {
-      const int r = 8 * fg + fq;
-      offB[ni] = r * 512 + (tm_slot(r, base / 8 + (fp >> 1)) << 4) + 8 * (fp & 1);
-    } else {
-      const int r = base + fi;
-      offB[ni] = r * 128;
-    }
-  }
-  auto frag = [&](const char* img, int off, int row_for_fm, int kk, auto is_fm) __attribute__((always_inline)) -> s16x8 {
-    if constexpr (!decltype(is_fm)::value) {
-      const lds_char* p = (const lds_char*)(img) + off + kk * 32 * 512;
-      const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p));
-      const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + 4 * 512));
-      return cat8(lo, hi);
-    } else {
-      const int slot = fm_slot(row_for_fm, fg + 4 * kk);
-      return *reinterpret_cast<const s16x8*>(img + off + (slot << 4));
-    }
-  };
-
-  f32x4 acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  if (nk > 0) issue(0);
-  if (nk > 1) issue(1);
-  for (int s = 0; s < nk; ++s) {
-    // this wave's 8 loads of step s done (step s + 1's 8 may stay in flight), then everyone's
-    if (s + 1 < nk) __builtin_amdgcn_s_waitcnt(0x0F78);   // vmcnt(8)
-    else __builtin_amdgcn_s_waitcnt(0x0F70);              // vmcnt(0)
-    __builtin_amdgcn_s_barrier();
-    const char* la = lds + (s & 1) * kStage;
-    const char* lb = la + kTileBytes;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      s16x8 af[8], bfr[4];
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni)
-        bfr[ni] = frag(lb, offB[ni], wc * 64 + ni * 16 + fi, kk, std::integral_constant<bool, kBFM>());
-#pragma unroll
-      for (int mi = 0; mi < 8; ++mi)
-        af[mi] = frag(la, offA[mi], wr * 128 + mi * 16 + fi, kk, std::integral_constant<bool, kAFM>());
-#pragma unroll
-      for (int mi = 0; mi < 8; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = mfma<T>(af[mi], bfr[ni], acc[mi][ni]);
-    }
-    __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): this wave's fragment reads are done
-    __builtin_amdgcn_s_barrier();         // ... and everyone's: the stage can be refilled
-    if (s + 2 < nk) issue(s + 2);
-  }
-
-  // ---- epilogue: fp32 tile (or this split's partial tile) -> C / slab.  acc[mi][ni] lane l holds
-  // rows 4 (l >> 4) + [0, 4) and column l & 15 of its 16 x 16 block.
-  float* C = g.C + (int64_t)split * g.slab_stride;
-#pragma unroll
-  for (int mi = 0; mi < 8; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) {
-      const int col = n0 + wc * 64 + ni * 16 + fi;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = m0 + wr * 128 + mi * 16 + 4 * fg + r;
-        if (row < g.M && col < g.N) C[(int64_t)row * g.ldc + col] = acc[mi][ni][r];
-      }
-    }
-}
-
 // ------------------------------------------------------------------ 4-phase-per-K-step pipeline
-// Same tile / waves / operand layouts as wgrad_kernel, but each 64-deep K step is split into four
-// phases of 16 MFMAs (one quadrant of a wave's 128 x 64 output: 64 x 32 over K 64), and the stage
-// is split into HALF-tiles by quadrant: A half qm = the rows {wr * 128 + qm * 64 + [0, 64)} of both
+// The main loop of mc_gemm_wgrad and mc_linear.  Each 64-deep K step is split into four phases of
+// 16 MFMAs (one quadrant of a wave's 128 x 64 output: 64 x 32 over K 64), and the stage is split
+// into HALF-tiles by quadrant: A half qm = the rows {wr * 128 + qm * 64 + [0, 64)} of both
 // wave rows, B half qn = the columns {wc * 64 + qn * 32 + [0, 32)} of the four wave columns.  Each
 // half is read in known phases only, so it is restaged for the step after next as soon as its last
 // reader phase has retired its reads (a barrier later), one half-tile (two glds per thread) per phase:
@@ -290,9 +139,10 @@ __device__ __forceinline__ void half_sources(const char* base, int64_t ld, int d
   }
 }
 
-// kStagger: the wave row wr = 1 runs one barrier behind wr = 0 (an extra s_barrier before the loop,
-// wr = 0 takes its extra one after it), so on every SIMD -- which holds one wave of each row -- one
-// wave's fragment reads overlap the other's MFMA cluster.  Each phase then retires its reads
+// kStagger (every launch but MC_WGRAD_PIPE=4): the wave rows are staggered, wr = 1 runs one barrier
+// behind wr = 0 (an extra s_barrier before the loop, wr = 0 takes its extra one after it), so on every
+// SIMD -- which holds one wave of each row -- one wave's fragment reads overlap the other's MFMA
+// cluster.  Each phase then retires its reads
 // (lgkmcnt(0)) BEFORE its first barrier: the half-tile restaged one phase later is only written after
 // that barrier, which both rows have passed with their reads of it done (cdna_hip_programming.md
 // section 5: "one barrier MORE when two wave groups run staggered").
@@ -510,8 +360,8 @@ __global__ __launch_bounds__(kThreads, 1) void wgrad4p_kernel(const Args g) {
 // 512 B (256 features), 16-B chunk c of row n at slot c ^ (n & 31).  A lane holds 4 consecutive
 // features of one token per accumulator (rows 4 (l >> 4) + r of the MFMA tile): one 8-B LDS write
 // each, the bias added before the rounding.  Then the workgroup walks the image row by row -- a
-// wave moves two whole 512-B rows -- and writes Y (and Y2 / reads H) with full-line 16-B accesses;
-// GELU / GELU' are evaluated there, on coalesced vectors.  The column sums (kEpiGeluGrad) meet in
+// wave moves two whole 512-B rows -- and writes Y (reading H) with full-line 16-B accesses;
+// GELU' is evaluated there, on coalesced vectors.  The column sums (kEpiGeluGrad) meet in
 // LDS in a fixed order: one fp32 partial per (token tile, feature), folded by the caller.
 template <typename T, int kEpi>
 __device__ __forceinline__ void epilogue16(const Args& g, char* lds, const f32x4 (&acc)[2][2][4][2], int m0, int n0,
@@ -536,7 +386,7 @@ __device__ __forceinline__ void epilogue16(const Args& g, char* lds, const f32x4
     for (int mi = 0; mi < 4; ++mi) {
       const int m = wr * 128 + qm * 64 + mi * 16 + 4 * fg;   // 4 consecutive features
       f32x4 b = f32x4{0.f, 0.f, 0.f, 0.f};
-      if constexpr (kEpi == kEpiBias || kEpi == kEpiBiasGelu) {
+      if constexpr (kEpi == kEpiBias) {
         if (m0 + m < g.M) {
           const uint2 bq = *reinterpret_cast<const uint2*>(reinterpret_cast<const T*>(g.bias) + m0 + m);
           const uint4 b4 = make_uint4(bq.x, bq.y, 0u, 0u);
@@ -593,12 +443,6 @@ __device__ __forceinline__ void epilogue16(const Args& g, char* lds, const f32x4
         const int t = n0 + (p0 + j) * 16 + sub;
         if (!fok || t >= g.N) continue;
         st16(reinterpret_cast<T*>(g.Y) + (int64_t)t * g.ldy + f, q[j]);
-        if constexpr (kEpi == kEpiBiasGelu) {
-          float o[8];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = gelu_f(elem_f<T>(q[j], e));   // library erff, torch's F.gelu form
-          st16(reinterpret_cast<T*>(g.Y2) + (int64_t)t * g.ldy2 + f, pack_f<T>(o));
-        }
       }
     }
   }
@@ -618,34 +462,24 @@ __device__ __forceinline__ void epilogue16(const Args& g, char* lds, const f32x4
   }
 }
 
-// MC_WGRAD_PIPE: 5 = four-phase pipeline with staggered wave rows (default), 4 = four-phase, rows in
-// step, 2 = wgrad_kernel (two barriers per K step)
+// MC_WGRAD_PIPE: 5 = staggered wave rows (default), 4 = rows in step (mc_gemm_wgrad only; kept with its tests)
 static int wgrad_pipe() {   // read per call: A/B runs flip it inside one process
   const char* e = getenv("MC_WGRAD_PIPE");
   return e ? atoi(e) : 5;
 }
 
+template <typename T, bool kStag>
+static void launch_ts(const Args& a, bool afm, bool bfm, hipStream_t s) {
+  const dim3 grid(a.tiles_m * a.tiles_n * a.splits), block(kThreads);
+  if (!afm && !bfm) hipLaunchKernelGGL((wgrad4p_kernel<T, false, false, kStag>), grid, block, 0, s, a);
+  else if (!afm && bfm) hipLaunchKernelGGL((wgrad4p_kernel<T, false, true, kStag>), grid, block, 0, s, a);
+  else if (afm && !bfm) hipLaunchKernelGGL((wgrad4p_kernel<T, true, false, kStag>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((wgrad4p_kernel<T, true, true, kStag>), grid, block, 0, s, a);
+}
 template <typename T>
 static void launch_t(const Args& a, bool afm, bool bfm, hipStream_t s) {
-  const dim3 grid(a.tiles_m * a.tiles_n * a.splits), block(kThreads);
-  if (wgrad_pipe() == 2) {
-    if (!afm && !bfm) hipLaunchKernelGGL((wgrad_kernel<T, false, false>), grid, block, 0, s, a);
-    else if (!afm && bfm) hipLaunchKernelGGL((wgrad_kernel<T, false, true>), grid, block, 0, s, a);
-    else if (afm && !bfm) hipLaunchKernelGGL((wgrad_kernel<T, true, false>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((wgrad_kernel<T, true, true>), grid, block, 0, s, a);
-    return;
-  }
-  if (wgrad_pipe() == 4) {
-    if (!afm && !bfm) hipLaunchKernelGGL((wgrad4p_kernel<T, false, false, false>), grid, block, 0, s, a);
-    else if (!afm && bfm) hipLaunchKernelGGL((wgrad4p_kernel<T, false, true, false>), grid, block, 0, s, a);
-    else if (afm && !bfm) hipLaunchKernelGGL((wgrad4p_kernel<T, true, false, false>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((wgrad4p_kernel<T, true, true, false>), grid, block, 0, s, a);
-    return;
-  }
-  if (!afm && !bfm) hipLaunchKernelGGL((wgrad4p_kernel<T, false, false, true>), grid, block, 0, s, a);
-  else if (!afm && bfm) hipLaunchKernelGGL((wgrad4p_kernel<T, false, true, true>), grid, block, 0, s, a);
-  else if (afm && !bfm) hipLaunchKernelGGL((wgrad4p_kernel<T, true, false, true>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((wgrad4p_kernel<T, true, true, true>), grid, block, 0, s, a);
+  if (wgrad_pipe() == 4) launch_ts<T, false>(a, afm, bfm, s);
+  else launch_ts<T, true>(a, afm, bfm, s);
 }
 
 static int auto_splits(int tiles, int nk) {
@@ -726,24 +560,14 @@ extern "C" int mc_gemm_wgrad(const mc_wgrad_params* p, void* stream) {
 // Y = X W^T on wgrad4p_kernel with both operands feature-major in its terms (A = W: row m = output
 // feature, B = X: row n = token, unit stride along K) and a 16-bit epilogue; one workgroup per
 // 256 x 256 output tile (K <= a few thousand: no split).
-template <typename T, bool kStag>
-static void launch_linear_s(const Args& a, int epi, hipStream_t s) {
-  const dim3 grid(a.tiles_m * a.tiles_n), block(kThreads);
-  switch (epi) {
-    case MC_LINEAR_EPI_NONE: hipLaunchKernelGGL((wgrad4p_kernel<T, true, true, kStag, kEpiStore>), grid, block, 0, s, a); break;
-    case MC_LINEAR_EPI_BIAS: hipLaunchKernelGGL((wgrad4p_kernel<T, true, true, kStag, kEpiBias>), grid, block, 0, s, a); break;
-    case MC_LINEAR_EPI_BIAS_GELU:
-      hipLaunchKernelGGL((wgrad4p_kernel<T, true, true, kStag, kEpiBiasGelu>), grid, block, 0, s, a);
-      break;
-    default: hipLaunchKernelGGL((wgrad4p_kernel<T, true, true, kStag, kEpiGeluGrad>), grid, block, 0, s, a); break;
-  }
-}
-// MC_LINEAR_STAGGER=0: wave rows in step (A/B of the staggered schedule at these short K loops)
 template <typename T>
 static void launch_linear(const Args& a, int epi, hipStream_t s) {
-  const char* e = getenv("MC_LINEAR_STAGGER");
-  if (e && atoi(e) == 0) launch_linear_s<T, false>(a, epi, s);
-  else launch_linear_s<T, true>(a, epi, s);
+  const dim3 grid(a.tiles_m * a.tiles_n), block(kThreads);
+  switch (epi) {
+    case MC_LINEAR_EPI_NONE: hipLaunchKernelGGL((wgrad4p_kernel<T, true, true, true, kEpiStore>), grid, block, 0, s, a); break;
+    case MC_LINEAR_EPI_BIAS: hipLaunchKernelGGL((wgrad4p_kernel<T, true, true, true, kEpiBias>), grid, block, 0, s, a); break;
+    default: hipLaunchKernelGGL((wgrad4p_kernel<T, true, true, true, kEpiGeluGrad>), grid, block, 0, s, a); break;
+  }
 }
 
 static int linear_check(const mc_linear_params* p) {
@@ -757,11 +581,9 @@ static int linear_check(const mc_linear_params* p) {
   MC_CHECK(ok(p->X, p->ldx, p->K) && ok(p->W, p->ldw, p->K) && ok(p->Y, p->ldy, p->cols), MC_ERR_SHAPE,
            "mc_linear: X, W, Y need 16-B aligned bases and leading dims %% 8 == 0 covering the row");
   MC_CHECK((int64_t)p->rows * std::max(p->ldx, p->ldy) < ((int64_t)1 << 40), MC_ERR_SHAPE, "mc_linear: operand too large");
-  if (p->epilogue == MC_LINEAR_EPI_BIAS || p->epilogue == MC_LINEAR_EPI_BIAS_GELU)
+  if (p->epilogue == MC_LINEAR_EPI_BIAS)
     MC_CHECK(p->bias && (reinterpret_cast<uintptr_t>(p->bias) & 7) == 0, MC_ERR_INVALID,
-             "mc_linear: the bias epilogues need an 8-B aligned bias (operand dtype)");
-  if (p->epilogue == MC_LINEAR_EPI_BIAS_GELU)
-    MC_CHECK(ok(p->Y2, p->ldy2, p->cols), MC_ERR_SHAPE, "mc_linear: BIAS_GELU needs Y2 (16-B aligned, ld %% 8 == 0)");
+             "mc_linear: the bias epilogue needs an 8-B aligned bias (operand dtype)");
   if (p->epilogue == MC_LINEAR_EPI_GELU_GRAD)
     MC_CHECK(ok(p->H, p->ldh, p->cols), MC_ERR_SHAPE, "mc_linear: GELU_GRAD needs H (16-B aligned, ld %% 8 == 0)");
   return MC_OK;
@@ -793,7 +615,7 @@ extern "C" int mc_linear(const mc_linear_params* p, void* stream) {
   a.tiles_m = (p->cols + kBM - 1) / kBM; a.tiles_n = tiles_n; a.nk = p->K / kBK;
   a.A = reinterpret_cast<const char*>(p->W); a.lda = p->ldw;
   a.B = reinterpret_cast<const char*>(p->X); a.ldb = p->ldx;
-  a.Y = p->Y; a.ldy = p->ldy; a.Y2 = p->Y2; a.ldy2 = p->ldy2; a.bias = p->bias;
+  a.Y = p->Y; a.ldy = p->ldy; a.bias = p->bias;
   a.H = p->H; a.ldh = p->ldh; a.colpart = sums ? reinterpret_cast<float*>(p->workspace) : nullptr;
   if (p->dtype == MC_DTYPE_BF16) launch_linear<bf16_t>(a, p->epilogue, s);
   else launch_linear<f16_t>(a, p->epilogue, s);

@@ -220,8 +220,7 @@ __device__ __forceinline__ float sigmoid_f(float x) { return fast_rcp(1.f + fast
 
 __device__ __forceinline__ float silu_f(float x) { return x * sigmoid_f(x); }
 
-// GELU, exact erf form (torch F.gelu approximate='none': x * 0.5 * (1 + erf(x / sqrt2))) and its derivative
-__device__ __forceinline__ float gelu_f(float x) { return x * 0.5f * (1.f + erff(x * 0.70710678118654752f)); }
+// derivative of GELU, exact erf form (torch F.gelu approximate='none': x * 0.5 * (1 + erf(x / sqrt2)))
 __device__ __forceinline__ float gelu_grad_f(float x) {   // d/dx [x * Phi(x)]
   const float cdf = 0.5f * (1.f + erff(x * 0.70710678118654752f));
   const float pdf = 0.39894228040143268f * __expf(-0.5f * x * x);

@@ -241,7 +241,7 @@ class WgradParams(ctypes.Structure):
     ]
 
 
-MC_LINEAR_EPI_NONE, MC_LINEAR_EPI_BIAS, MC_LINEAR_EPI_BIAS_GELU, MC_LINEAR_EPI_GELU_GRAD = 0, 1, 2, 3
+MC_LINEAR_EPI_NONE, MC_LINEAR_EPI_BIAS, MC_LINEAR_EPI_GELU_GRAD = 0, 1, 2
 
 
 class LinearParams(ctypes.Structure):
@@ -249,7 +249,7 @@ class LinearParams(ctypes.Structure):
     _fields_ = [
         ("rows", c_i32), ("cols", c_i32), ("K", c_i32), ("dtype", c_i32), ("epilogue", c_i32), ("reserved", c_i32),
         ("X", c_vp), ("ldx", c_i64), ("W", c_vp), ("ldw", c_i64), ("Y", c_vp), ("ldy", c_i64),
-        ("Y2", c_vp), ("ldy2", c_i64), ("bias", c_vp), ("H", c_vp), ("ldh", c_i64), ("colsum", c_vp),
+        ("bias", c_vp), ("H", c_vp), ("ldh", c_i64), ("colsum", c_vp),
         ("workspace", c_vp), ("workspace_bytes", ctypes.c_size_t),
     ]
 

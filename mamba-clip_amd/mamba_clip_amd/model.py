@@ -23,7 +23,6 @@ add+RMSNorm / add+LayerNorm, patch im2col, short-sequence attention
 (attention.hip), contrastive loss; dense projections are plain library GEMMs
 (hipBLASLt through torch, launched data-parallel: see __init__.py).
 """
-import contextlib
 import math
 import os
 from functools import partial
@@ -659,12 +658,11 @@ class ClipModel(nn.Module):
             return None
         return self.side_stream_for(image.device)
 
-    def _towers_two_streams(self, image, text, side, main, dt=None):
-        """(image_features, text_features) with the side tower on `side`.  With dt, each tower runs in its own
-        weight-cast scope entered on its own stream; without (shared_weight_casts), the caller's scope
-        serves both."""
+    def _towers_two_streams(self, image, text, side, main, dt):
+        """(image_features, text_features) with the side tower on `side`.  Each tower runs in its own
+        weight-cast scope (a no-op outside autocast, dt None) entered on its own stream."""
         def scope(module):
-            return weight_cast_scope(module, dt) if dt is not None else contextlib.nullcontext()
+            return weight_cast_scope(module, dt)
         if self.side_tower == "image":
             image.record_stream(side)
             with torch.cuda.stream(side), scope(self.visual):
@@ -691,11 +689,6 @@ class ClipModel(nn.Module):
         f = self.text(text)
         return l2_normalize(f) if normalize else f
 
-    # A/B switch (round 4 behaviour): one weight-cast buffer for both towers, made on the main stream and
-    # handed to the side stream with record_stream.  Off: each tower casts its own weights on its own stream
-    # (DESIGN 4.9), so no buffer crosses the streams in either direction.
-    shared_weight_casts = os.environ.get("MAMBA_CLIP_AMD_SHARED_WEIGHT_CASTS", "0") == "1"
-
     def forward(self, image, text, secondary_text=None):
         # under CUDA autocast: the towers' Linear weights cast to 16 bits in one launch per tower and forward
         # (ops.weight_cast_scope) instead of one cast per weight and use
@@ -706,15 +699,6 @@ class ClipModel(nn.Module):
             with weight_cast_scope(self, dt):
                 image_features = self.encode_image(image, normalize=True) if image is not None else None
                 text_features = self.encode_text(text, normalize=True) if text is not None else None
-                if secondary_text is not None:
-                    secondary = self.encode_text(secondary_text, normalize=True)
-        elif self.shared_weight_casts:
-            with weight_cast_scope(self, dt) as casts:
-                main = torch.cuda.current_stream()
-                self.last_main_stream = main
-                side.wait_stream(main)
-                casts.record_stream(side)
-                image_features, text_features = self._towers_two_streams(image, text, side, main)
                 if secondary_text is not None:
                     secondary = self.encode_text(secondary_text, normalize=True)
         else:

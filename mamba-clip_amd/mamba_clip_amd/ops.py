@@ -19,7 +19,6 @@ All launches go on the current HIP stream; nothing synchronises.
 """
 import collections
 import ctypes
-import os
 import weakref
 
 import torch
@@ -987,21 +986,11 @@ def wgrad_hip(G, X, splits=0):
     return out
 
 
-# The towers' long-K weight gradients on mc_gemm_wgrad (csrc/gemm_wgrad.hip, on by default since round 5:
-# 1.0-1.1 PFLOP/s vs the library split-K slabs' 0.75-0.91 at the ViT / Mamba shapes, same-box step
-# C2 69.96 -> 68.5 ms, C3 25.4 -> 25.0 ms, profiles/r05/wgrad/); 0 = the library slabs (A/B)
-WGRAD_HIP = os.environ.get("MAMBA_CLIP_AMD_WGRAD_HIP", "1") != "0"
-
-
-def wgrad(G, X):
-    """G @ X in fp32 for G (N, M), X (M, K), any strides, M the long reduction dim."""
+def wgrad_slabs(G, X):
+    """G @ X in fp32 for G (N, M), X (M, K), any strides, on the library: one mm, or for a long M on the
+    GPU a strided-batched GEMM over _split_factor slabs of M and mc_sum_slabs."""
     N, M = G.shape
     K = X.shape[1]
-    if WGRAD_HIP and G.is_cuda and M >= 8192 and min(N, K) >= 256:
-        # (the skinny x_proj / dt_proj outputs, 80 and 48 wide, stay on the library: 25 vs 47 us at C2)
-        out = wgrad_hip(G, X)
-        if out is not None:
-            return out
     s = _split_factor(M, N, K) if (G.is_cuda and M >= 8192) else 1
     if s == 1:
         return torch.mm(G, X).float()
@@ -1013,6 +1002,19 @@ def wgrad(G, X):
     _lib.check(_lib.load().mc_sum_slabs(s, N * K, part.data_ptr(), part.stride(0), out.data_ptr(),
                                         _lib.stream_handle(part.device)), "mc_sum_slabs")
     return out
+
+
+def wgrad(G, X):
+    """G @ X in fp32 for G (N, M), X (M, K), any strides, M the long reduction dim.  The towers' long-M
+    weight gradients run on mc_gemm_wgrad (1.0-1.1 PFLOP/s vs the library slabs' 0.75-0.91 at the ViT /
+    Mamba shapes: DESIGN 4.3, profiles/r05/wgrad/); the skinny x_proj / dt_proj outputs (80 and 48 wide:
+    25 vs 47 us at C2), short reductions and operands outside the kernel's layouts take the library."""
+    N, M = G.shape
+    if M >= 8192 and min(N, X.shape[1]) >= 256:
+        out = wgrad_hip(G, X)
+        if out is not None:
+            return out
+    return wgrad_slabs(G, X)
 
 
 def colsum(x):
@@ -1250,7 +1252,7 @@ def _wcast_t(weight, x, dt):
     """The 16-bit transposed copy of `weight` for the "tn" input gradient (_dgrad) when that form
     applies to x @ weight^T, served from the active weight_cast_scope; None when the form does not
     apply or the scope has no copy yet (the weight is then registered, and the next scope casts it)."""
-    if not (DGRAD_TN and WCAST_T and x.is_cuda and weight.dim() == 2 and weight.numel() >= 1 << 19
+    if not (x.is_cuda and weight.dim() == 2 and weight.numel() >= 1 << 19
             and x.numel() // max(x.shape[-1], 1) >= 8192):
         return None
     if _WCAST_T is not None:
@@ -1293,13 +1295,6 @@ class weight_cast_scope:
 
     def __init__(self, module, dt):
         self.module, self.dt, self.active = module, dt, False
-        self.buf = self.buf_t = None
-
-    def record_stream(self, stream):
-        """The copies are used on another stream too (ClipModel's concurrent towers)."""
-        for b in (self.buf, self.buf_t):
-            if b is not None:
-                b.record_stream(stream)
 
     def __enter__(self):
         global _WCAST, _WCAST_T
@@ -1316,7 +1311,6 @@ class weight_cast_scope:
             plan = (key, _CastPlan(params, self.dt, params[0].device))
             _CAST_PLANS[key[:2]] = plan
         copies = plan[1].run(params)
-        self.buf = copies[0]
         _WCAST = {id(p): (p, c) for p, c in zip(params, copies)}
         tparams = [p for p in params if p.dim() == 2 and _T_WANTED.get(id(p)) is p]
         if tparams:
@@ -1326,7 +1320,6 @@ class weight_cast_scope:
                 tplan = (tkey, _TransposePlan(tparams, self.dt, params[0].device))
                 _CAST_PLANS[tkey[:3]] = tplan
             tcopies = tplan[1].run(tparams)
-            self.buf_t = tcopies[0]
             _WCAST_T = {id(p): (p, c) for p, c in zip(tparams, tcopies)}
         self.active = True
         return self
@@ -1344,34 +1337,14 @@ class weight_cast_scope:
 # the tuning file (tuning/gemm_gfx950_dp.csv).  The transposed 16-bit copies come from the forward's
 # weight_cast_scope (mc_cast_transpose_f32_many, one launch for all of them: _wcast_t); a per-call
 # transpose of the 16-bit copy (~40 us each for the ViT's fc weights) is only the first step's
-# fallback.  A/B toggle.
-DGRAD_TN = os.environ.get("MAMBA_CLIP_AMD_DGRAD_TN", "1") != "0"
-WCAST_T = os.environ.get("MAMBA_CLIP_AMD_WCAST_T", "1") != "0"     # A/B: scope copies vs per-call transposes
-
-
-# The remaining towers' Linear forward / input-gradient GEMMs (qkv, proj, patch embedding, the MLP's
-# fc1 input gradient) on mc_linear instead of the library: A/B toggles.
-LINEAR_HIP_FWD = os.environ.get("MAMBA_CLIP_AMD_LINEAR_HIP_FWD", "0") == "1"
-LINEAR_HIP_DGRAD = os.environ.get("MAMBA_CLIP_AMD_LINEAR_HIP_DGRAD", "0") == "1"
-
-
-def _fwd_gemm(xc, wc, bc):
-    """F.linear(xc, wc, bc), on mc_linear (bias epilogue) when LINEAR_HIP_FWD and the shapes qualify."""
-    if LINEAR_HIP_FWD and xc.is_cuda and xc.dim() >= 2 and (bc is None or bc.dtype == xc.dtype):
-        x2 = xc.reshape(-1, xc.shape[-1])
-        if x2.shape[0] >= 8192 and linear_hip_ok(x2, wc):
-            return linear_hip(x2, wc, bc).view(*xc.shape[:-1], wc.shape[0])
-    return torch.nn.functional.linear(xc, wc, bc)
-
-
+# fallback.  These GEMMs, and the forward of every Linear but the MLP's fc2, stay on the library:
+# mc_linear was measured at both and lost.
 def _dgrad(g2, wc, wt=None):
     """g2 (M, N) @ wc (N, K) for a row-major weight copy wc (wt: its transposed copy, or None)."""
-    if LINEAR_HIP_DGRAD and wt is not None and g2.shape[0] >= 8192 and linear_hip_ok(g2, wt):
-        return linear_hip(g2, wt)
     if wt is not None:
         return torch.mm(g2, wt.t())
-    if DGRAD_TN and g2.is_cuda and g2.shape[0] >= 8192 and wc.shape[0] * wc.shape[1] >= 1 << 19:
-        return torch.mm(g2, wc.t().contiguous().t())
+    if g2.is_cuda and g2.shape[0] >= 8192 and wc.shape[0] * wc.shape[1] >= 1 << 19:
+        return torch.mm(g2, wc.t().contiguous().t())   # large weight, no copy yet: the per-call transpose
     return torch.mm(g2, wc)
 
 
@@ -1390,7 +1363,7 @@ class LinearSK(torch.autograd.Function):
         xc, wc = x.to(dt), _wcast(weight, dt)
         bc = _wcast(bias, dt) if bias is not None else None
         with torch.autocast("cuda", enabled=False):
-            y = _fwd_gemm(xc, wc, bc)
+            y = torch.nn.functional.linear(xc, wc, bc)
         ctx.save_for_backward(xc, wc)
         ctx.has_bias = bias is not None
         colmajor = xc.dim() == 2 and xc.stride(0) == 1 and xc.stride(1) != 1
@@ -1424,13 +1397,10 @@ def linear_sk(x, weight, bias=None):
 
 
 # w @ X with a short reduction (the mixer's dt_proj forward, K = dt_rank) on mc_gemm_small_k instead of
-# the library GEMM.  A/B toggle.
-SMALL_K_HIP = os.environ.get("MAMBA_CLIP_AMD_SMALL_K_HIP", "1") != "0"
-
-
+# the library GEMM.
 def small_k_ok(wc, Xc):
     K = wc.shape[1]
-    return (SMALL_K_HIP and Xc.is_cuda and wc.dtype == Xc.dtype and Xc.dtype in (torch.bfloat16, torch.float16)
+    return (Xc.is_cuda and wc.dtype == Xc.dtype and Xc.dtype in (torch.bfloat16, torch.float16)
             and K in (16, 32, 48, 64) and Xc.shape[1] % 8 == 0 and Xc.stride(1) == 1 and Xc.stride(0) % 8 == 0
             and Xc.data_ptr() % 16 == 0 and wc.stride(1) == 1 and wc.stride(0) % 4 == 0 and wc.data_ptr() % 8 == 0)
 
@@ -1511,10 +1481,9 @@ def _hip_rows(t, V, who):
 
 
 # ---------------------------------------------------------------------------- towers' Linears on mc_linear
-# The forward / input-gradient GEMMs of the ViT Linears on the hand-written 256 x 256 kernel
-# (csrc/gemm_wgrad.hip, mc_linear) with the epilogues the library cannot fuse: bias + exact-erf GELU
-# for fc1 (one pass writes h and gelu(h)) and GELU' for fc2's input gradient (one pass writes
-# gh = ga * gelu'(h) and fc1's bias gradient).
+# The ViT MLP's fc2 forward and its two input-gradient GEMMs on the hand-written 256 x 256 kernel
+# (csrc/gemm_wgrad.hip, mc_linear): a bias epilogue, and GELU' for fc2's input gradient, which the
+# library cannot fuse (one pass writes gh = ga * gelu'(h) and fc1's bias gradient).
 
 
 def linear_hip_ok(x2, w):
@@ -1529,7 +1498,7 @@ def linear_hip_ok(x2, w):
 
 def linear_hip(x2, w, bias=None, epilogue=None, h=None, want_colsum=False):
     """x2 @ w^T on mc_linear with a fused epilogue (include/mc_gemm.h):
-    NONE / BIAS -> y; BIAS_GELU -> (h, gelu(h)); GELU_GRAD (h = the pre-activation) -> (gh, colsum or None).
+    NONE / BIAS -> y; GELU_GRAD (h = the pre-activation) -> (gh, colsum or None).
     The caller checks linear_hip_ok; a launch error raises (no library fallback inside)."""
     if epilogue is None:
         epilogue = _lib.MC_LINEAR_EPI_BIAS if bias is not None else _lib.MC_LINEAR_EPI_NONE
@@ -1539,14 +1508,11 @@ def linear_hip(x2, w, bias=None, epilogue=None, h=None, want_colsum=False):
     p = _lib.LinearParams()
     p.rows, p.cols, p.K, p.dtype, p.epilogue = rows, cols, K, _lib.dtype_code(x2.dtype), epilogue
     p.X, p.ldx, p.W, p.ldw, p.Y, p.ldy = x2.data_ptr(), x2.stride(0), w.data_ptr(), w.stride(0), y.data_ptr(), cols
-    y2 = colsum_out = None
+    colsum_out = None
     if bias is not None:
         if bias.dtype != x2.dtype or bias.stride(0) != 1 or bias.data_ptr() % 8:
             bias = bias.to(x2.dtype).contiguous()
         p.bias = bias.data_ptr()
-    if epilogue == _lib.MC_LINEAR_EPI_BIAS_GELU:
-        y2 = torch.empty_like(y)
-        p.Y2, p.ldy2 = y2.data_ptr(), cols
     ws = None
     if epilogue == _lib.MC_LINEAR_EPI_GELU_GRAD:
         h = _hip_rows(h, 8, "linear_hip GELU_GRAD")
@@ -1560,22 +1526,16 @@ def linear_hip(x2, w, bias=None, epilogue=None, h=None, want_colsum=False):
         ws = _ws(ws_b, x2.device)
         p.workspace, p.workspace_bytes = ws.data_ptr(), ws_b
     _lib.check(lib.mc_linear(ctypes.byref(p), _lib.stream_handle(x2.device)), "mc_linear")
-    if epilogue == _lib.MC_LINEAR_EPI_BIAS_GELU:
-        return y, y2
     if epilogue == _lib.MC_LINEAR_EPI_GELU_GRAD:
         return y, colsum_out
     return y
 
 
-# which MLP passes run on mc_linear (A/B toggles, tools/ab_step.py --toggle ops.MLP_HIP_FC1 ...):
-#   FC1: fc1 + bias + GELU in one epilogue; FC2: fc2 + bias; BWD: fc2's input gradient times GELU' with
-#   fc1's bias gradient in one epilogue, and fc1's input gradient.  Off: the library GEMM of that pass
-#   (+ the standalone GELU / mc_gelu_bwd passes).  Measured in DESIGN 4.3 (round 5, same-box C2 step
-#   A/B, profiles/r05/linear/): BWD -0.35..-0.52 ms (4 of 4 reps), FC2 -0.04..-0.35 ms (3 of 3) -- on;
-#   FC1 +0.07..+0.44 ms (its un-overlapped GELU epilogue costs more than the pass it saves) -- off.
-MLP_HIP_FC1 = os.environ.get("MAMBA_CLIP_AMD_MLP_HIP_FC1", "0") == "1"
-MLP_HIP_FC2 = os.environ.get("MAMBA_CLIP_AMD_MLP_HIP_FC2", "1") == "1"
-MLP_HIP_BWD = os.environ.get("MAMBA_CLIP_AMD_MLP_HIP_BWD", "1") == "1"
+# Which MLP passes run on mc_linear (measured in DESIGN 4.3, same-box C2 step A/B, profiles/r05/linear/):
+# fc2's forward with its bias (-0.04..-0.35 ms per step) and the backward -- fc2's input gradient times
+# GELU' with fc1's bias gradient in one epilogue, and fc1's input gradient (-0.35..-0.52 ms).  fc1 and its
+# GELU stay on the library GEMM and torch's GELU: a fused fc1 + GELU epilogue cost more un-overlapped
+# than the pass it saved (+0.07..+0.44 ms) and was removed.
 
 
 def _gelu_bwd(h2, g2):
@@ -1596,12 +1556,14 @@ def _gelu_bwd(h2, g2):
 
 class MlpFn(torch.autograd.Function):
     """y = fc2(gelu(fc1(x))) -- the ViT block's MLP (timm Mlp: fc1 -> nn.GELU() exact erf -> fc2; the
-    reference's image tower, model.py:1011-1017), each pass on mc_linear or the library per the
-    MLP_HIP_* toggles:
-      forward:  (h, a) = fc1 + bias + GELU in one epilogue;  y = a @ w2^T + b2
-      backward: gh = (gy @ w2) * gelu'(h) with fc1's bias gradient in one epilogue (no standalone
-                GELU-backward pass, no stored fc2 input gradient);  dx = gh @ w1;  dW1, dW2 on
-                mc_gemm_wgrad;  db2 = column sums of gy.
+    reference's image tower, model.py:1011-1017):
+      forward:  h = fc1 on the library GEMM, a = F.gelu(h);  y = a @ w2^T + b2 on mc_linear
+      backward: gh = (gy @ w2) * gelu'(h) with fc1's bias gradient in one mc_linear epilogue (no
+                standalone GELU-backward pass, no stored fc2 input gradient);  dx = gh @ w1 on
+                mc_linear;  dW1, dW2 by wgrad;  db2 = column sums of gy.
+    Each mc_linear call is guarded by linear_hip_ok (the strides / 16-B alignment the kernel needs); an
+    ineligible operand takes the fallback instead of failing the step: the library GEMM for y and dx,
+    _dgrad + mc_gelu_bwd for gh.
     Same roundings as the unfused chain: h, a, y, ga (inside the epilogue) and gh once each in the
     activation dtype."""
 
@@ -1612,14 +1574,9 @@ class MlpFn(torch.autograd.Function):
         w1c, b1c, w2c, b2c = _wcast(w1, dt), _wcast(b1, dt), _wcast(w2, dt), _wcast(b2, dt)
         x2 = xc.reshape(-1, xc.shape[-1])
         with torch.autocast("cuda", enabled=False):
-            # each mc_linear call is guarded by linear_hip_ok (strides / 16-B alignment the kernel needs);
-            # an ineligible operand takes the library GEMM instead of failing the step
-            if MLP_HIP_FC1 and linear_hip_ok(x2, w1c):
-                h, a = linear_hip(x2, w1c, b1c, _lib.MC_LINEAR_EPI_BIAS_GELU)
-            else:
-                h = torch.nn.functional.linear(x2, w1c, b1c)
-                a = torch.nn.functional.gelu(h)
-            y = (linear_hip(a, w2c, b2c) if MLP_HIP_FC2 and linear_hip_ok(a, w2c)
+            h = torch.nn.functional.linear(x2, w1c, b1c)
+            a = torch.nn.functional.gelu(h)
+            y = (linear_hip(a, w2c, b2c) if linear_hip_ok(a, w2c)
                  else torch.nn.functional.linear(a, w2c, b2c))
         ctx.save_for_backward(x2, h, a, w1c, w2c)
         ctx.wt1, ctx.wt2 = _wcast_t(w1, xc, dt), _wcast_t(w2, a, dt)
@@ -1634,16 +1591,16 @@ class MlpFn(torch.autograd.Function):
             g2 = g2.contiguous()
         db2 = _bias_grad(gy, g2)
         dw2 = wgrad(g2.t(), a)
-        wt2 = (ctx.wt2 if ctx.wt2 is not None else w2c.t().contiguous()) if MLP_HIP_BWD else None
-        if MLP_HIP_BWD and linear_hip_ok(g2, wt2) and _aligned_rows(h, 8):
+        wt2 = ctx.wt2 if ctx.wt2 is not None else w2c.t().contiguous()
+        if linear_hip_ok(g2, wt2) and _aligned_rows(h, 8):
             gh, db1 = linear_hip(g2, wt2, None, _lib.MC_LINEAR_EPI_GELU_GRAD, h=h, want_colsum=True)
         else:
             gh, db1 = _gelu_bwd(h, _dgrad(g2, w2c, ctx.wt2))
         dw1 = wgrad(gh.t(), x2)
         dx = None
         if ctx.needs_input_grad[0]:
-            wt1 = (ctx.wt1 if ctx.wt1 is not None else w1c.t().contiguous()) if MLP_HIP_BWD else None
-            if MLP_HIP_BWD and linear_hip_ok(gh, wt1):
+            wt1 = ctx.wt1 if ctx.wt1 is not None else w1c.t().contiguous()
+            if linear_hip_ok(gh, wt1):
                 dx = linear_hip(gh, wt1)
             else:
                 dx = _dgrad(gh, w1c, ctx.wt1)
@@ -1661,7 +1618,7 @@ def mlp_hip_ok(x, w1, b1, w2, b2):
 
 def mlp(x, w1, b1, w2, b2):
     """ViT MLP y = fc2(gelu(fc1(x))): MlpFn on the GPU, else fc1_gelu + linear_sk."""
-    if (MLP_HIP_FC1 or MLP_HIP_FC2 or MLP_HIP_BWD) and mlp_hip_ok(x, w1, b1, w2, b2):
+    if mlp_hip_ok(x, w1, b1, w2, b2):
         return MlpFn.apply(x, w1, b1, w2, b2)
     return linear_sk(fc1_gelu(x, w1, b1), w2, b2)
 
@@ -1718,7 +1675,7 @@ class QKVProjFn(torch.autograd.Function):
         xc, wc, bc = x.to(dt), _wcast(weight, dt), _wcast(bias, dt)
         Bsz, N, C = xc.shape
         with torch.autocast("cuda", enabled=False):
-            y = _fwd_gemm(xc, wc, bc)
+            y = torch.nn.functional.linear(xc, wc, bc)
         ctx.save_for_backward(xc, wc)
         ctx.heads = heads
         ctx.wt = _wcast_t(weight, xc, dt)

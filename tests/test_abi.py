@@ -148,7 +148,8 @@ def test_attention_validation_without_launch():
                                           ("mc_ss2d_merge_params", "SS2DMergeParams"),
                                           ("mc_ss2d_merge_bwd_params", "SS2DMergeBwdParams"),
                                           ("mc_patch_input_params", "PatchInputParams"),
-                                          ("mc_wgrad_params", "WgradParams")])
+                                          ("mc_wgrad_params", "WgradParams"),
+                                          ("mc_linear_params", "LinearParams")])
 def test_struct_layout_matches_header(cname, pyname):
     from mamba_clip_amd import _lib
     cls = getattr(_lib, pyname)

@@ -14,7 +14,7 @@ Variants (comma list, --variants):
   conc_fsync two streams, device synchronize after forward only
   conc_torchadam  two streams, torch's fused AdamW instead of HipAdamW
   conc_text two streams, text tower on the side stream
-  conc_nowt two streams, no transposed weight copies (ops.WCAST_T off)
+Every variant runs the default GEMM paths (mc_gemm_wgrad, the scope's transposed weight copies).
 Run once as is and once with PYTORCH_NO_CUDA_MEMORY_CACHING=1 to separate allocator-reuse hazards
 (a missing record_stream) from ordering hazards (a missing wait)."""
 import argparse
@@ -36,7 +36,7 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--variants", default="conc,seq,conc_sync,conc_torchadam,conc_text,conc_nowt")
+    ap.add_argument("--variants", default="conc,seq,conc_sync,conc_torchadam,conc_text")
     ap.add_argument("--out", default=None)
     ap.add_argument("--compare", choices=["first", "prev"], default="first",
                     help="compare each run with the first run overall, or with the previous run of its variant")
@@ -62,10 +62,10 @@ def main():
         torch.utils.deterministic.fill_uninitialized_memory = True
 
     from types import SimpleNamespace
-    from mamba_clip_amd import ops, train
+    from mamba_clip_amd import train
     from mamba_clip_amd.data import synthetic_batch
     from mamba_clip_amd.loss import ClipLoss
-    from mamba_clip_amd.model import ClipModel, build_clip
+    from mamba_clip_amd.model import build_clip
     from mamba_clip_amd.tuning import load_gemm_tuning
     from mamba_clip_amd.utils.amp_utils import get_autocast
 
@@ -172,10 +172,7 @@ def main():
         for m in model.modules():
             if hasattr(m, "fused_attention"):
                 m.fused_attention = not variant.endswith("_noattn")
-        ops.WGRAD_HIP = variant.endswith("_wgradhip")
         torch.backends.cuda.preferred_blas_library("cublas" if variant.endswith("_rocblas") else "cublaslt")
-        ops.WCAST_T = variant != "conc_nowt"
-        ClipModel.shared_weight_casts = variant.endswith("_sharedcast")
         hip = train.HIP_ADAMW
         train.HIP_ADAMW = variant != "conc_torchadam"
         opt = train.create_optimizer(model, targs)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Same-process A/B of the towers' weight-gradient GEMMs at the C2 shapes: the library split-K slabs
-(ops.wgrad with MAMBA_CLIP_AMD_WGRAD_HIP off: bmm(out_dtype=fp32) + mc_sum_slabs) vs mc_gemm_wgrad
-(csrc/gemm_wgrad.hip), HIP events, interleaved rounds; plus a split-count sweep of the HIP kernel.
+(ops.wgrad_slabs: bmm(out_dtype=fp32) + mc_sum_slabs) vs mc_gemm_wgrad (ops.wgrad_hip,
+csrc/gemm_wgrad.hip), HIP events, interleaved rounds; plus a split-count sweep of the HIP kernel.
 Prints one JSON line per shape: us and TFLOP/s per arm, max |diff| relative to max |ref|."""
 import json
 import os
@@ -62,15 +62,9 @@ def main():
             continue
         G, X = operands(N, K, T, a_fm, b_fm)
         flop = 2.0 * N * K * T
-        ops.WGRAD_HIP = False
-        lib_us = timed(lambda: ops.wgrad(G, X))
-        ref = ops.wgrad(G, X)
-        pipes = {}
-        for pipe in ("2", "4", "5"):
-            os.environ["MC_WGRAD_PIPE"] = pipe
-            pipes[pipe] = round(timed(lambda: ops.wgrad_hip(G, X)), 1)
-        os.environ["MC_WGRAD_PIPE"] = "5"
-        hip_us = pipes["5"]
+        lib_us = timed(lambda: ops.wgrad_slabs(G, X))
+        ref = ops.wgrad_slabs(G, X)
+        hip_us = timed(lambda: ops.wgrad_hip(G, X))
         out = ops.wgrad_hip(G, X)
         err = float((out - ref).abs().max() / ref.abs().max())
         sweep = {}
@@ -79,8 +73,7 @@ def main():
                 sweep[s] = round(timed(lambda: ops.wgrad_hip(G, X, splits=s), iters=10, rounds=3), 1)
         print(json.dumps({"shape": name, "N": N, "K": K, "T": T, "lib_us": round(lib_us, 1), "hip_us": round(hip_us, 1),
                           "lib_tflops": round(flop / lib_us / 1e6, 1), "hip_tflops": round(flop / hip_us / 1e6, 1),
-                          "rel_err_vs_lib": err, "pipe_us": pipes,
-                          "hip_split_sweep_us": sweep}), flush=True)
+                          "rel_err_vs_lib": err, "hip_split_sweep_us": sweep}), flush=True)
 
 
 if __name__ == "__main__":
