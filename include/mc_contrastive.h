@@ -72,31 +72,6 @@ int32_t mc_gemm_nt_kernel(const mc_gemm_nt_params* p);
 int mc_quant_rows_fp8(int32_t rows, int32_t cols, int32_t in_dtype, const void* X, int64_t ldx, uint8_t* Q,
                       int64_t ldq, float* inv_scale, void* stream);
 
-/* Softmax cross-entropy statistics along the rows (axis = 0: one value per
- * row, reduce over columns) or the columns (axis = 1) of an fp32 matrix S
- * (rows x cols, leading dimension lds):
- *   lse[i]     = log sum_j exp(S[i, j])            (row i; or column i for axis 1)
- *   nll[i]     = lse[i] - S[i, label_i]            label_i = i + label_offset
- * loss_out (device scalar, nullable) = sum_i nll[i] * loss_coef. */
-int mc_ce_stats(int32_t rows, int32_t cols, const float* S, int64_t lds, int32_t axis, int64_t label_offset,
-                float* lse, float* nll, float loss_coef, float* loss_out, void* workspace, size_t workspace_bytes,
-                void* stream);
-size_t mc_ce_stats_workspace_bytes(int32_t rows, int32_t cols, int32_t axis);
-
-/* Gradient of  coef_r * sum_i nll_row[i] + coef_c * sum_j nll_col[j]  w.r.t. S,
- * times the upstream scalar *gout_dev:
- *   G[i, j] = gout * ( coef_r * (exp(S_ij - lse_r[i]) - [j == i + off_r])
- *                    + coef_c * (exp(S_ij - lse_c[j]) - [i == j + off_c]) )
- * (lse_c == NULL drops the column term).  G is written in out_dtype
- * (fp32 / bf16).  If dscale_out != NULL it also accumulates
- * sum_ij G_ij * S_ij / scale (scale = *scale_dev): the gradient of the loss
- * w.r.t. logit_scale, deterministic two-pass reduction in workspace. */
-int mc_ce_grad(int32_t rows, int32_t cols, const float* S, int64_t lds, const float* lse_r, int64_t off_r,
-               float coef_r, const float* lse_c, int64_t off_c, float coef_c, const float* gout_dev,
-               int32_t out_dtype, void* G, int64_t ldg, const float* scale_dev, float* dscale_out, void* workspace,
-               size_t workspace_bytes, void* stream);
-size_t mc_ce_grad_workspace_bytes(int32_t rows, int32_t cols);
-
 /* Fused logits + softmax cross-entropy (no M x N matrix in memory).
  *   S[i, j] = scale * sx[i] * sy[j] * sum_k X[i, k] Y[j, k]        (never stored)
  *   loss    = coef_r * sum_i (lse_r[i] - S[i, i + row_off])

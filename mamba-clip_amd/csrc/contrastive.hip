@@ -18,11 +18,10 @@
 //    registers and run the bf16 MFMA instead (exact fp32 accumulation).  alpha may live on the device (logit_scale.exp()), so the loss
 //    needs no host sync.
 //  * quant_rows_fp8: one wave per row, amax -> 448/amax scale -> v_cvt_pk_fp8_f32.
-//  * ce_rows / ce_cols(+finalize): log-sum-exp statistics and per-label NLL
-//    along rows or columns, online max/sum, deterministic fixed-order
-//    partial reductions (no atomics).
-//  * ce_grad: fused softmax-minus-onehot gradient for the row and column CE
-//    terms in one pass, plus the logit_scale gradient sum(G*S)/scale.
+//  * fused logits + CE (mc_ce_fused_fwd / _grad): the GEMM tiles reduce their logits in registers to
+//    per-row / per-column log-sum-exp partials and label logits (online max/sum), folded in a fixed
+//    order (no atomics); the gradient sweep recomputes the tiles and writes softmax-minus-onehot for
+//    the row and column CE terms in one pass, plus the logit_scale gradient sum(G*S)/scale.
 //  * retrieval ranks (mc_retrieval_ranks): the whole-set image <-> text ranks the
 //    reference's evaluate stops short of (eval.py:65-66: the n x n product of the
 //    accumulated features "will blow up memory"), for the similarity of
@@ -38,7 +37,6 @@
 //    folds them.  Gradient: kEpi 5 writes coef * (sigmoid(z) - [label]) through the GEMM's store
 //    epilogue and reduces the logit_scale / logit_bias gradients per tile.  No atomics.
 #include <algorithm>
-#include <cstdlib>
 
 #include "mc_common.h"
 #include "../../include/mc_contrastive.h"
@@ -1095,96 +1093,7 @@ __global__ __launch_bounds__(512, 1) void sim8_panel_kernel(const GemmArgs g, in
   }
 }
 
-// ------------------------------------------------------------------ CE statistics
-
-// one wave per row: lse and nll, per-block partial NLL sums (4 rows per block)
-__global__ __launch_bounds__(256) void ce_rows_kernel(int rows, int cols, const float* __restrict__ S, int64_t lds,
-                                                      int64_t off, float* __restrict__ lse, float* __restrict__ nll,
-                                                      float* __restrict__ partial) {
-  __shared__ float pn[4];
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + w;
-  float v = 0.f;
-  if (row < rows) {
-    const float* sr = S + (int64_t)row * lds;
-    float m = -INFINITY, s = 0.f;
-    for (int j = lane; j < cols; j += 64) {
-      const float x = sr[j];
-      if (x > m) { s = s * __expf(m - x) + 1.f; m = x; }
-      else s += __expf(x - m);
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-      const float m2 = __shfl_xor(m, o), s2 = __shfl_xor(s, o);
-      lse_merge(m, s, m2, s2);
-    }
-    const float l = m + __logf(s);
-    const int64_t lab = row + off;
-    const float tgt = (lab >= 0 && lab < cols) ? sr[lab] : 0.f;
-    v = l - tgt;
-    if (lane == 0) {
-      lse[row] = l;
-      if (nll) nll[row] = v;
-    }
-  }
-  if (lane == 0) pn[w] = row < rows ? v : 0.f;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = (pn[0] + pn[1]) + (pn[2] + pn[3]);
-}
-
-// columns: block = 64 columns x 4 row lanes, grid.y = row splits; writes (m, s) partials
-__global__ __launch_bounds__(256) void ce_cols_partial_kernel(int rows, int cols, const float* __restrict__ S,
-                                                              int64_t lds, int splits, float2* __restrict__ part) {
-  __shared__ float2 red[4][64];
-  const int cx = threadIdx.x & 63, q = threadIdx.x >> 6;
-  const int col = blockIdx.x * 64 + cx;
-  const int per = (rows + splits - 1) / splits;
-  const int r0 = blockIdx.y * per, r1 = min(rows, r0 + per);
-  float m = -INFINITY, s = 0.f;
-  if (col < cols) {
-    for (int r = r0 + q; r < r1; r += 4) {
-      const float x = S[(int64_t)r * lds + col];
-      if (x > m) { s = s * __expf(m - x) + 1.f; m = x; }
-      else s += __expf(x - m);
-    }
-  }
-  red[q][cx] = make_float2(m, s);
-  __syncthreads();
-  if (q == 0 && col < cols) {
-#pragma unroll
-    for (int k = 1; k < 4; ++k) lse_merge(m, s, red[k][cx].x, red[k][cx].y);
-    part[(int64_t)blockIdx.y * cols + col] = make_float2(m, s);
-  }
-}
-
-__global__ __launch_bounds__(256) void ce_cols_final_kernel(int rows, int cols, const float* __restrict__ S,
-                                                            int64_t lds, int splits, const float2* __restrict__ part,
-                                                            int64_t off, float* __restrict__ lse,
-                                                            float* __restrict__ nll, float* __restrict__ partial) {
-  __shared__ float pn[256];
-  const int col = blockIdx.x * 256 + threadIdx.x;
-  float v = 0.f;
-  if (col < cols) {
-    float m = -INFINITY, s = 0.f;
-    for (int k = 0; k < splits; ++k) {
-      const float2 p = part[(int64_t)k * cols + col];
-      lse_merge(m, s, p.x, p.y);
-    }
-    const float l = m + __logf(s);
-    const int64_t lab = col + off;
-    const float tgt = (lab >= 0 && lab < rows) ? S[lab * lds + col] : 0.f;
-    v = l - tgt;
-    lse[col] = l;
-    if (nll) nll[col] = v;
-  }
-  pn[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = 128; o >= 1; o >>= 1) {
-    if ((int)threadIdx.x < o) pn[threadIdx.x] += pn[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[blockIdx.x] = pn[0];
-}
+// ------------------------------------------------------------------ folds of the fused sweeps' tile partials
 
 // fixed-order sum of n partials -> out[0] = coef * sum  (one block)
 __global__ __launch_bounds__(256) void sum_partials_kernel(const float* __restrict__ part, int n, float coef,
@@ -1267,35 +1176,6 @@ __global__ __launch_bounds__(256) void rank_fold_kernel(int M, int N, int tiles_
   (rows ? eq_r : eq_c)[idx] = eq;
 }
 
-// G = gout * (coef_r (softmax_r - onehot_r) + coef_c (softmax_c - onehot_c)); partial sum(G * S)
-template <typename TOut>
-__global__ __launch_bounds__(256) void ce_grad_kernel(int rows, int cols, const float* __restrict__ S, int64_t lds,
-                                                      const float* __restrict__ lse_r, int64_t off_r, float coef_r,
-                                                      const float* __restrict__ lse_c, int64_t off_c, float coef_c,
-                                                      const float* __restrict__ gout_dev, TOut* __restrict__ G,
-                                                      int64_t ldg, float* __restrict__ partial) {
-  __shared__ float red[256];
-  const float gout = gout_dev ? *gout_dev : 1.f;
-  const int64_t total = (int64_t)rows * cols;
-  float acc = 0.f;
-  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
-    const int i = (int)(idx / cols), j = (int)(idx % cols);
-    const float s = S[(int64_t)i * lds + j];
-    float gv = coef_r * (__expf(s - lse_r[i]) - ((int64_t)j == i + off_r ? 1.f : 0.f));
-    if (lse_c) gv += coef_c * (__expf(s - lse_c[j]) - ((int64_t)i == j + off_c ? 1.f : 0.f));
-    gv *= gout;
-    G[(int64_t)i * ldg + j] = from_f<TOut>(gv);
-    acc = fmaf(gv, s, acc);
-  }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = 128; o >= 1; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && partial) partial[blockIdx.x] = red[0];
-}
-
 // ------------------------------------------------------------------ fp8 quantiser
 constexpr float kFp8Max = 448.f;   // e4m3fn max finite
 
@@ -1329,9 +1209,6 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(int rows, int cols,
   }
 }
 
-constexpr int kColSplits = 32;
-constexpr int kGradGrid = 2048;
-
 }  // namespace ctr
 }  // namespace mc
 
@@ -1358,15 +1235,10 @@ void launch_gemm(const GemmArgs& g, int in_dtype, int out_dtype, bool aligned, h
 }
 
 // The panel kernel's eligibility: K % 64 == 0, K <= 512; whole 16-B output vectors (N % 8, ldc % 8 and a
-// 16-B aligned C); 32-bit buffer offsets over the output.  MAMBA_CLIP_AMD_SIM8_PANEL=0 keeps the
-// 128 x 128 tile kernel (A/B).
+// 16-B aligned C); 32-bit buffer offsets over the output.
 bool sim8_panel_ok(const GemmArgs& g, const mc_gemm_nt_params* p) {
-  static const bool on = [] {
-    const char* e = getenv("MAMBA_CLIP_AMD_SIM8_PANEL");
-    return !(e && e[0] == '0');
-  }();
   const int es = p->out_dtype == MC_DTYPE_F32 ? 4 : 2;
-  return on && p->K > 0 && p->K % 64 == 0 && p->K <= kP8Row && p->N % 8 == 0 && p->ldc % 8 == 0 && aligned16(p->C) &&
+  return p->K > 0 && p->K % 64 == 0 && p->K <= kP8Row && p->N % 8 == 0 && p->ldc % 8 == 0 && aligned16(p->C) &&
          (int64_t)p->M * p->ldc * es < ((int64_t)1 << 31);
 }
 
@@ -1383,12 +1255,7 @@ void launch_sim8_panel_t(const GemmArgs& g0, hipStream_t s) {
   // interleaved n-ranges for fp32 logits (C5: 87 -> 70 us, the 8 n-ranges of a panel write one 2-KB row
   // piece per tile step instead of eight 256-B pieces 4 KB apart); bf16 logits keep contiguous ranges
   // (51.6 vs 60 us in a launch loop, equal under graph replay: profiles/r06/c5/interleave_ab.txt).
-  // MAMBA_CLIP_AMD_SIM8_INTERLEAVE=0 / 1 forces either (A/B).
-  static const int env_ilv = [] {
-    const char* e = getenv("MAMBA_CLIP_AMD_SIM8_INTERLEAVE");
-    return e ? (e[0] == '0' ? 0 : 1) : -1;
-  }();
-  const int ilv = env_ilv >= 0 ? env_ilv : (sizeof(TOut) == 4 ? 1 : 0);
+  const int ilv = sizeof(TOut) == 4 ? 1 : 0;
   switch (g.K / 64) {
 #define MC_P8(NK) case NK: hipLaunchKernelGGL((sim8_panel_kernel<TOut, NK>), grid, block, 0, s, g, nr, tpr, ilv); break;
     MC_P8(1) MC_P8(2) MC_P8(3) MC_P8(4) MC_P8(5) MC_P8(6) MC_P8(7) MC_P8(8)
@@ -1463,74 +1330,6 @@ extern "C" int mc_gemm_nt(const mc_gemm_nt_params* p, void* stream) {
   }
   const hipError_t e = hipGetLastError();
   MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "mc_gemm_nt: launch failed: %s", hipGetErrorString(e));
-  return MC_OK;
-}
-
-extern "C" size_t mc_ce_stats_workspace_bytes(int32_t rows, int32_t cols, int32_t axis) {
-  if (rows <= 0 || cols <= 0) return 0;
-  if (axis == 0) return (size_t)((rows + 3) / 4) * sizeof(float);
-  return (size_t)kColSplits * cols * sizeof(float2) + (size_t)((cols + 255) / 256) * sizeof(float) + 256;
-}
-
-extern "C" int mc_ce_stats(int32_t rows, int32_t cols, const float* S, int64_t lds, int32_t axis,
-                           int64_t label_offset, float* lse, float* nll, float loss_coef, float* loss_out,
-                           void* workspace, size_t workspace_bytes, void* stream) {
-  MC_CHECK(rows > 0 && cols > 0, MC_ERR_SHAPE, "mc_ce_stats: empty matrix");
-  MC_CHECK(axis == 0 || axis == 1, MC_ERR_INVALID, "mc_ce_stats: axis must be 0 (rows) or 1 (columns)");
-  MC_CHECK(S && lse, MC_ERR_INVALID, "mc_ce_stats: null S / lse");
-  const size_t need = mc_ce_stats_workspace_bytes(rows, cols, axis);
-  MC_CHECK(workspace && workspace_bytes >= need && aligned16(workspace), MC_ERR_WORKSPACE,
-           "mc_ce_stats: workspace must be >= %zu bytes, 16-B aligned", need);
-  hipStream_t s = (hipStream_t)stream;
-  if (axis == 0) {
-    const int nb = (rows + 3) / 4;
-    float* part = reinterpret_cast<float*>(workspace);
-    hipLaunchKernelGGL(ce_rows_kernel, dim3(nb), dim3(256), 0, s, rows, cols, S, lds, label_offset, lse, nll, part);
-    if (loss_out) hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, part, nb, loss_coef, nullptr, loss_out);
-  } else {
-    float2* part = reinterpret_cast<float2*>(workspace);
-    float* lpart = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + (size_t)kColSplits * cols * sizeof(float2));
-    const int splits = std::min(kColSplits, rows);
-    hipLaunchKernelGGL(ce_cols_partial_kernel, dim3((cols + 63) / 64, splits), dim3(256), 0, s, rows, cols, S, lds,
-                       splits, part);
-    const int nb = (cols + 255) / 256;
-    hipLaunchKernelGGL(ce_cols_final_kernel, dim3(nb), dim3(256), 0, s, rows, cols, S, lds, splits, part,
-                       label_offset, lse, nll, lpart);
-    if (loss_out) hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, lpart, nb, loss_coef, nullptr, loss_out);
-  }
-  const hipError_t e = hipGetLastError();
-  MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "mc_ce_stats: launch failed: %s", hipGetErrorString(e));
-  return MC_OK;
-}
-
-extern "C" size_t mc_ce_grad_workspace_bytes(int32_t rows, int32_t cols) {
-  (void)rows; (void)cols;
-  return (size_t)kGradGrid * sizeof(float);
-}
-
-extern "C" int mc_ce_grad(int32_t rows, int32_t cols, const float* S, int64_t lds, const float* lse_r, int64_t off_r,
-                          float coef_r, const float* lse_c, int64_t off_c, float coef_c, const float* gout_dev,
-                          int32_t out_dtype, void* G, int64_t ldg, const float* scale_dev, float* dscale_out,
-                          void* workspace, size_t workspace_bytes, void* stream) {
-  MC_CHECK(rows > 0 && cols > 0, MC_ERR_SHAPE, "mc_ce_grad: empty matrix");
-  MC_CHECK(S && lse_r && G, MC_ERR_INVALID, "mc_ce_grad: null S / lse_r / G");
-  MC_CHECK(out_dtype == MC_DTYPE_F32 || out_dtype == MC_DTYPE_BF16, MC_ERR_DTYPE, "mc_ce_grad: G must be fp32/bf16");
-  MC_CHECK(!dscale_out || (workspace && workspace_bytes >= mc_ce_grad_workspace_bytes(rows, cols)), MC_ERR_WORKSPACE,
-           "mc_ce_grad: workspace too small for the logit_scale gradient");
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t total = (int64_t)rows * cols;
-  const int grid = (int)std::min<int64_t>((total + 255) / 256, kGradGrid);
-  float* part = dscale_out ? reinterpret_cast<float*>(workspace) : nullptr;
-  if (out_dtype == MC_DTYPE_F32)
-    hipLaunchKernelGGL((ce_grad_kernel<float>), dim3(grid), dim3(256), 0, s, rows, cols, S, lds, lse_r, off_r, coef_r,
-                       lse_c, off_c, coef_c, gout_dev, reinterpret_cast<float*>(G), ldg, part);
-  else
-    hipLaunchKernelGGL((ce_grad_kernel<bf16_t>), dim3(grid), dim3(256), 0, s, rows, cols, S, lds, lse_r, off_r,
-                       coef_r, lse_c, off_c, coef_c, gout_dev, reinterpret_cast<bf16_t*>(G), ldg, part);
-  if (dscale_out)
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, part, grid, 1.f, scale_dev, dscale_out);
-  const hipError_t e = hipGetLastError();
-  MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "mc_ce_grad: launch failed: %s", hipGetErrorString(e));
   return MC_OK;
 }
 

@@ -26,13 +26,13 @@
 //    distinct 16-B bank slots; as sim_fp8_kernel).
 // Tile 256 x 256 x 64, 8 waves as 2 (m) x 4 (n), 128 x 64 per wave on v_mfma_f32_16x16x32_{bf16,f16}
 // (32 accumulators); one loop, wgrad4p_kernel: four phases per K step over half-tile images, the two
-// wave rows one barrier apart (kStagger), 128 KB of LDS (two stages of four 16-KB half-tiles), the
-// next steps' loads in flight across the MFMAs (counted vmcnt, raw s_barrier), one workgroup per CU.
+// wave rows one barrier apart, 128 KB of LDS (two stages of four 16-KB half-tiles), the next steps'
+// loads in flight across the MFMAs (counted vmcnt, raw s_barrier), one workgroup per CU.
 //
 // The same loop with a 16-bit epilogue is mc_linear (Y = X W^T, optionally + bias or * gelu'(H)); the
 // short-K mc_gemm_small_k at the end of the file is a separate kernel.  The two-barrier loop this one
-// replaced and the fc1 + GELU epilogue were measured and removed; the rows-in-step
-// schedule (kStagger = false) survives for mc_gemm_wgrad behind MC_WGRAD_PIPE=4, with its tests.
+// replaced, the schedule with both wave rows in step and the fc1 + GELU epilogue were measured and
+// removed.
 #include <type_traits>
 
 #include "mc_common.h"
@@ -139,10 +139,9 @@ __device__ __forceinline__ void half_sources(const char* base, int64_t ld, int d
   }
 }
 
-// kStagger (every launch but MC_WGRAD_PIPE=4): the wave rows are staggered, wr = 1 runs one barrier
-// behind wr = 0 (an extra s_barrier before the loop, wr = 0 takes its extra one after it), so on every
-// SIMD -- which holds one wave of each row -- one wave's fragment reads overlap the other's MFMA
-// cluster.  Each phase then retires its reads
+// The wave rows are staggered: wr = 1 runs one barrier behind wr = 0 (an extra s_barrier before the
+// loop, wr = 0 takes its extra one after it), so on every SIMD -- which holds one wave of each row --
+// one wave's fragment reads overlap the other's MFMA cluster.  Each phase therefore retires its reads
 // (lgkmcnt(0)) BEFORE its first barrier: the half-tile restaged one phase later is only written after
 // that barrier, which both rows have passed with their reads of it done (cdna_hip_programming.md
 // section 5: "one barrier MORE when two wave groups run staggered").
@@ -152,7 +151,7 @@ template <typename T, int kEpi>
 __device__ __forceinline__ void epilogue16(const Args& g, char* lds, const f32x4 (&acc)[2][2][4][2], int m0, int n0,
                                            int tn, int wr, int wc, int fg, int fi, int tid, const uint4 (&hpre)[kHPre]);
 
-template <typename T, bool kAFM, bool kBFM, bool kStagger, int kEpi = kEpiSlab>
+template <typename T, bool kAFM, bool kBFM, int kEpi = kEpiSlab>
 __global__ __launch_bounds__(kThreads, 1) void wgrad4p_kernel(const Args g) {
   __shared__ __attribute__((aligned(16))) char lds[2 * 4 * kHalf];   // [stage][A h0, A h1, B h0, B h1]
   const int tid = threadIdx.x, lane = tid & 63;
@@ -256,13 +255,8 @@ __global__ __launch_bounds__(kThreads, 1) void wgrad4p_kernel(const Args g) {
     __builtin_amdgcn_s_setprio(0);
   };
   auto sync_reads = [&]() __attribute__((always_inline)) {
-    if constexpr (kStagger) {
-      __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0) first: the reads are retired before the barrier
-      __builtin_amdgcn_s_barrier();
-    } else {
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): this phase's fragment reads are in
-    }
+    __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0) first: the reads are retired before the barrier
+    __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
   };
 
@@ -282,7 +276,7 @@ __global__ __launch_bounds__(kThreads, 1) void wgrad4p_kernel(const Args g) {
   __builtin_amdgcn_s_barrier();
 
   s16x8 af[4][2], bf0[2][2], bf1[2][2];
-  if (kStagger && wr == 1) __builtin_amdgcn_s_barrier();   // wr is wave-uniform (readfirstlane'd w)
+  if (wr == 1) __builtin_amdgcn_s_barrier();   // wr is wave-uniform (readfirstlane'd w)
   // kEpiGeluGrad: the epilogue's first H vectors are requested at the start of the last K step, so their
   // latency hides behind its MFMAs (nothing else is in flight then: the step before retired with vmcnt(0))
   uint4 hpre[kHPre];
@@ -329,7 +323,7 @@ __global__ __launch_bounds__(kThreads, 1) void wgrad4p_kernel(const Args g) {
     mma_q(1, 0, af, bf0);
     __builtin_amdgcn_s_barrier();
   }
-  if (kStagger && wr == 0) __builtin_amdgcn_s_barrier();   // equal barrier counts for both rows
+  if (wr == 0) __builtin_amdgcn_s_barrier();   // equal barrier counts for both rows
 
   if constexpr (kEpi != kEpiSlab) {
     epilogue16<T, kEpi>(g, lds, acc, m0, n0, tn, wr, wc, fg, fi, tid, hpre);
@@ -462,24 +456,13 @@ __device__ __forceinline__ void epilogue16(const Args& g, char* lds, const f32x4
   }
 }
 
-// MC_WGRAD_PIPE: 5 = staggered wave rows (default), 4 = rows in step (mc_gemm_wgrad only; kept with its tests)
-static int wgrad_pipe() {   // read per call: A/B runs flip it inside one process
-  const char* e = getenv("MC_WGRAD_PIPE");
-  return e ? atoi(e) : 5;
-}
-
-template <typename T, bool kStag>
-static void launch_ts(const Args& a, bool afm, bool bfm, hipStream_t s) {
-  const dim3 grid(a.tiles_m * a.tiles_n * a.splits), block(kThreads);
-  if (!afm && !bfm) hipLaunchKernelGGL((wgrad4p_kernel<T, false, false, kStag>), grid, block, 0, s, a);
-  else if (!afm && bfm) hipLaunchKernelGGL((wgrad4p_kernel<T, false, true, kStag>), grid, block, 0, s, a);
-  else if (afm && !bfm) hipLaunchKernelGGL((wgrad4p_kernel<T, true, false, kStag>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((wgrad4p_kernel<T, true, true, kStag>), grid, block, 0, s, a);
-}
 template <typename T>
 static void launch_t(const Args& a, bool afm, bool bfm, hipStream_t s) {
-  if (wgrad_pipe() == 4) launch_ts<T, false>(a, afm, bfm, s);
-  else launch_ts<T, true>(a, afm, bfm, s);
+  const dim3 grid(a.tiles_m * a.tiles_n * a.splits), block(kThreads);
+  if (!afm && !bfm) hipLaunchKernelGGL((wgrad4p_kernel<T, false, false>), grid, block, 0, s, a);
+  else if (!afm && bfm) hipLaunchKernelGGL((wgrad4p_kernel<T, false, true>), grid, block, 0, s, a);
+  else if (afm && !bfm) hipLaunchKernelGGL((wgrad4p_kernel<T, true, false>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((wgrad4p_kernel<T, true, true>), grid, block, 0, s, a);
 }
 
 static int auto_splits(int tiles, int nk) {
@@ -564,9 +547,9 @@ template <typename T>
 static void launch_linear(const Args& a, int epi, hipStream_t s) {
   const dim3 grid(a.tiles_m * a.tiles_n), block(kThreads);
   switch (epi) {
-    case MC_LINEAR_EPI_NONE: hipLaunchKernelGGL((wgrad4p_kernel<T, true, true, true, kEpiStore>), grid, block, 0, s, a); break;
-    case MC_LINEAR_EPI_BIAS: hipLaunchKernelGGL((wgrad4p_kernel<T, true, true, true, kEpiBias>), grid, block, 0, s, a); break;
-    default: hipLaunchKernelGGL((wgrad4p_kernel<T, true, true, true, kEpiGeluGrad>), grid, block, 0, s, a); break;
+    case MC_LINEAR_EPI_NONE: hipLaunchKernelGGL((wgrad4p_kernel<T, true, true, kEpiStore>), grid, block, 0, s, a); break;
+    case MC_LINEAR_EPI_BIAS: hipLaunchKernelGGL((wgrad4p_kernel<T, true, true, kEpiBias>), grid, block, 0, s, a); break;
+    default: hipLaunchKernelGGL((wgrad4p_kernel<T, true, true, kEpiGeluGrad>), grid, block, 0, s, a); break;
   }
 }
 

@@ -285,12 +285,6 @@ SYMBOLS = {
     "mc_gemm_nt": (ctypes.c_int, [ctypes.POINTER(GemmNTParams), c_vp]),
     "mc_gemm_nt_kernel": (c_i32, [ctypes.POINTER(GemmNTParams)]),
     "mc_quant_rows_fp8": (ctypes.c_int, [c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_i64, c_fp, c_vp]),
-    "mc_ce_stats": (ctypes.c_int, [c_i32, c_i32, c_fp, c_i64, c_i32, c_i64, c_fp, c_fp, ctypes.c_float, c_fp,
-                                   c_vp, ctypes.c_size_t, c_vp]),
-    "mc_ce_stats_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32]),
-    "mc_ce_grad": (ctypes.c_int, [c_i32, c_i32, c_fp, c_i64, c_fp, c_i64, ctypes.c_float, c_fp, c_i64,
-                                  ctypes.c_float, c_fp, c_i32, c_vp, c_i64, c_fp, c_fp, c_vp, ctypes.c_size_t, c_vp]),
-    "mc_ce_grad_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32]),
     "mc_ce_fused_fwd": (ctypes.c_int, [ctypes.POINTER(CEFusedParams), c_vp]),
     "mc_ce_fused_fwd_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32]),
     "mc_ce_fused_grad": (ctypes.c_int, [ctypes.POINTER(CEFusedParams), c_vp]),

@@ -49,9 +49,6 @@ def _dt_bias_init(d_inner, dt_min=0.001, dt_max=0.1, dt_init_floor=1e-4):
     return dt + torch.log(-torch.expm1(-dt))
 
 
-XPROJ_GRAD_SLAB = os.environ.get("MAMBA_CLIP_AMD_XPROJ_GRAD_SLAB", "1") != "0"   # A/B toggle
-
-
 def mixer_scan(x, delta, A, Bm, Cm, D, z, delta_bias, dz_slab, du_handoff=None, dbc_slab=None):
     """The mixer's scan call (selective_scan_fn semantics, softplus on) with dz written into
     the in_proj gradient slab, dB / dC into the x_proj gradient slab and du handed to x_proj's
@@ -115,8 +112,7 @@ class MambaMixer(nn.Module):
         x_dbl = wleft_mm(self.x_proj.weight, x_cm, hand)                   # (R+2N, B*L)
         # dt_proj's backward writes d(dt_raw) and the scan's writes dB / dC straight into one
         # (R+2N, B*L) gradient slab: no transpose copies of dB / dC, no concatenation
-        pslab = GradSlab(R + 2 * N, Bsz * L, x_dbl.dtype, x_dbl.device) if (x_dbl.requires_grad and
-                                                                             XPROJ_GRAD_SLAB) else None
+        pslab = GradSlab(R + 2 * N, Bsz * L, x_dbl.dtype, x_dbl.device) if x_dbl.requires_grad else None
         dt_raw, Bm, Cm = split_rows_n(x_dbl, (R, N, N), pslab)
         delta = wleft_mm(self.dt_proj.weight, dt_raw, out_slab=(pslab, 0) if pslab is not None else None)
         delta = delta.view(di, Bsz, L).transpose(0, 1)
@@ -611,28 +607,13 @@ class ClipModel(nn.Module):
     def side_priority(self):
         """HIP priority of the text-tower stream (-1 high, 0 normal, 1 low where the device has it):
         high beside the BERT tower (C3 25.3 -> 25.0 ms per step), normal beside the Mamba tower
-        (C2 69.9 -> 70.8 ms at high); profiles/r04/stream_priority/.  MAMBA_CLIP_AMD_SIDE_PRIORITY
-        overrides (A/B)."""
-        env = os.environ.get("MAMBA_CLIP_AMD_SIDE_PRIORITY")
-        if env is not None:
-            return int(env)
+        (C2 69.9 -> 70.8 ms at high); profiles/r04/stream_priority/."""
         return -1 if isinstance(self.text, (BertTextEncoder, HFBertTextEncoder)) else 0
 
-    @property
-    def side_tower(self):
-        """Which tower runs on the side stream: the text tower, for every text tower.  Round 4 put the
-        image tower there beside the Mamba text tower (C2 -0.3 ms, profiles/r04/stream_priority/); in
-        round 5 that arrangement was not run-to-run reproducible (the scan backward's packed op_sel
-        broadcast, found and removed in round 6) and the two measured the same on one box
-        (3683 vs 3684 pairs/s), so the text tower stays on the side stream.  MAMBA_CLIP_AMD_SIDE_TOWER=
-        image restores the other arrangement for A/B."""
-        env = os.environ.get("MAMBA_CLIP_AMD_SIDE_TOWER")
-        if env in ("text", "image"):
-            return env
-        return "text"
-
     def side_tower_module(self):
-        return self.visual if self.side_tower == "image" else self.text
+        """The tower that runs on the side stream: the text tower, for every text tower (the image
+        tower there measured the same on one box).  train.wrap_ddp probes for this method."""
+        return self.text
 
     def side_stream_for(self, device):
         device = torch.device(device)
@@ -659,26 +640,15 @@ class ClipModel(nn.Module):
         return self.side_stream_for(image.device)
 
     def _towers_two_streams(self, image, text, side, main, dt):
-        """(image_features, text_features) with the side tower on `side`.  Each tower runs in its own
+        """(image_features, text_features) with the text tower on `side`.  Each tower runs in its own
         weight-cast scope (a no-op outside autocast, dt None) entered on its own stream."""
-        def scope(module):
-            return weight_cast_scope(module, dt)
-        if self.side_tower == "image":
-            image.record_stream(side)
-            with torch.cuda.stream(side), scope(self.visual):
-                image_features = self.encode_image(image, normalize=True)
-            with scope(self.text):
-                text_features = self.encode_text(text, normalize=True)
-            main.wait_stream(side)
-            image_features.record_stream(main)
-        else:
-            text.record_stream(side)
-            with torch.cuda.stream(side), scope(self.text):
-                text_features = self.encode_text(text, normalize=True)
-            with scope(self.visual):
-                image_features = self.encode_image(image, normalize=True)
-            main.wait_stream(side)
-            text_features.record_stream(main)
+        text.record_stream(side)
+        with torch.cuda.stream(side), weight_cast_scope(self.text, dt):
+            text_features = self.encode_text(text, normalize=True)
+        with weight_cast_scope(self.visual, dt):
+            image_features = self.encode_image(image, normalize=True)
+        main.wait_stream(side)
+        text_features.record_stream(main)
         return image_features, text_features
 
     def encode_image(self, image, normalize: bool = False):

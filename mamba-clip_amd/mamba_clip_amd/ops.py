@@ -1,5 +1,6 @@
-"""Thin torch-facing wrappers of the contrastive kernels (include/mc_contrastive.h).
+"""Thin torch-facing wrappers of the library's kernels (include/*.h), one section per header.
 
+Contrastive ops (include/mc_contrastive.h), at the head of the file:
 ``gemm_nt(A, B, alpha)``  C = alpha * A @ B.T on the matrix cores (bf16, fp32 or fp8 e4m3fn in).
 ``quant_rows_fp8(X)``     row-wise amax-scaled e4m3fn quantisation (K padded to 16).
 ``similarity_fp8(I, T, scale)``  scale * I @ T.T through the fp8 MFMA path (config 5).
@@ -10,11 +11,13 @@
                           the logits never exist in memory (mc_ce_fused_*).
 ``sigmoid_logits_loss``   autograd op: the pairwise sigmoid (SigLIP) loss of
                           scale * X @ Y.T + bias, fused the same way (mc_sigmoid_loss_*).
-``ce_stats`` / ``ce_grad`` the unfused statistics / gradient kernels over a
-                          materialised S (kept for logits the caller needs anyway).
 ``retrieval_ranks(X, Y, scale)``  evaluation: per-row / per-column counts of logits that beat or
                           tie the label's, plus LSE and loss, again without the logits in
                           memory (mc_retrieval_ranks).
+Then the encoder ops (mc_ops.h: the fused norms, causal conv1d, patch im2col, L2 normalisation, the
+per-forward weight casts), the towers' projections (mc_gemm.h: ``wgrad``, ``linear_sk``, ``wleft_mm``,
+``linear_hip``, ``mlp``, ``qkv_proj``), the packed short-sequence attention (mc_attn.h) and the SS2D
+cross-scan glue (mc_ss2d.h).  The selective scan has its own module (selective_scan_interface.py).
 All launches go on the current HIP stream; nothing synchronises.
 """
 import collections
@@ -124,37 +127,6 @@ def clip_loss_fp8(image_features, text_features, logit_scale):
           else torch.tensor(float(logit_scale), device=qi.device)).contiguous()
     loss, _, _ = ce_fused_fwd(qi, qt, sc, 0, 0.5 / n, 0, 0.5 / n, sx=si, sy=st)
     return loss
-
-
-def ce_stats(S, axis, label_offset, coef):
-    """(lse, weighted NLL sum as a device scalar) along rows (axis 0) or columns (1)."""
-    lib = _lib.load()
-    rows, cols = S.shape
-    n = rows if axis == 0 else cols
-    lse = torch.empty(n, device=S.device, dtype=torch.float32)
-    loss = torch.empty((), device=S.device, dtype=torch.float32)
-    ws_b = lib.mc_ce_stats_workspace_bytes(rows, cols, axis)
-    ws = _ws(ws_b, S.device)
-    _lib.check(lib.mc_ce_stats(rows, cols, S.data_ptr(), S.stride(0), axis, int(label_offset), lse.data_ptr(),
-                               None, float(coef), loss.data_ptr(), ws.data_ptr(), ws_b,
-                               _lib.stream_handle(S.device)), "mc_ce_stats")
-    return lse, loss
-
-
-def ce_grad(S, lse_r, off_r, coef_r, lse_c, off_c, coef_c, gout, out_dtype, scale):
-    """G = gout * d(loss)/dS (fp32 or bf16) and d(loss)/d(scale) (device scalar)."""
-    lib = _lib.load()
-    rows, cols = S.shape
-    G = torch.empty(rows, cols, device=S.device, dtype=out_dtype)
-    dscale = torch.empty((), device=S.device, dtype=torch.float32)
-    ws_b = lib.mc_ce_grad_workspace_bytes(rows, cols)
-    ws = _ws(ws_b, S.device)
-    gout = gout.reshape(()).float().contiguous()
-    _lib.check(lib.mc_ce_grad(rows, cols, S.data_ptr(), S.stride(0), lse_r.data_ptr(), int(off_r), float(coef_r),
-                              lse_c.data_ptr() if lse_c is not None else None, int(off_c), float(coef_c),
-                              gout.data_ptr(), _lib.dtype_code(out_dtype), G.data_ptr(), cols, scale.data_ptr(),
-                              dscale.data_ptr(), ws.data_ptr(), ws_b, _lib.stream_handle(S.device)), "mc_ce_grad")
-    return G, dscale
 
 
 # G blocks of the fused backward hold at most this many elements (32 MiB bf16):

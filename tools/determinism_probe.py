@@ -12,8 +12,6 @@ Variants (comma list, --variants):
   seq       one stream
   conc_sync two streams, device synchronize after forward and after backward
   conc_fsync two streams, device synchronize after forward only
-  conc_torchadam  two streams, torch's fused AdamW instead of HipAdamW
-  conc_text two streams, text tower on the side stream
 Every variant runs the default GEMM paths (mc_gemm_wgrad, the scope's transposed weight copies).
 Run once as is and once with PYTORCH_NO_CUDA_MEMORY_CACHING=1 to separate allocator-reuse hazards
 (a missing record_stream) from ordering hazards (a missing wait)."""
@@ -36,7 +34,7 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--variants", default="conc,seq,conc_sync,conc_torchadam,conc_text")
+    ap.add_argument("--variants", default="conc,seq,conc_sync")
     ap.add_argument("--out", default=None)
     ap.add_argument("--compare", choices=["first", "prev"], default="first",
                     help="compare each run with the first run overall, or with the previous run of its variant")
@@ -161,22 +159,14 @@ def main():
         model.load_state_dict(init)
         model.zero_grad(set_to_none=True)
         model.concurrent_towers = not variant.startswith("seq")
-        os.environ.pop("MAMBA_CLIP_AMD_SIDE_TOWER", None)
         os.environ.pop("MAMBA_CLIP_AMD_FINE_STATES_MB", None)
-        if variant.startswith("conc_text"):
-            os.environ["MAMBA_CLIP_AMD_SIDE_TOWER"] = "text"
-        elif variant.startswith("conc_image"):
-            os.environ["MAMBA_CLIP_AMD_SIDE_TOWER"] = "image"
         if variant.endswith("_nofine"):
             os.environ["MAMBA_CLIP_AMD_FINE_STATES_MB"] = "0"
         for m in model.modules():
             if hasattr(m, "fused_attention"):
                 m.fused_attention = not variant.endswith("_noattn")
         torch.backends.cuda.preferred_blas_library("cublas" if variant.endswith("_rocblas") else "cublaslt")
-        hip = train.HIP_ADAMW
-        train.HIP_ADAMW = variant != "conc_torchadam"
         opt = train.create_optimizer(model, targs)
-        train.HIP_ADAMW = hip
         rec = {}
         losses = []
         from mamba_clip_amd import selective_scan_interface as ssi

@@ -22,15 +22,12 @@ def main():
     ap.add_argument("--model", default="vit_b16-mamba130m")
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--steps", type=int, default=3)
-    ap.add_argument("--side-tower", default=None)
     args = ap.parse_args()
     alloc = torch.cuda.memory.CUDAPluggableAllocator(SO, "guard_malloc", "guard_free")
     torch.cuda.memory.change_current_allocator(alloc)
     lib = ctypes.CDLL(SO)
     lib.guard_report.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_int]
     lib.guard_check_live.argtypes = [ctypes.c_void_p]
-    if args.side_tower:
-        os.environ["MAMBA_CLIP_AMD_SIDE_TOWER"] = args.side_tower
     from types import SimpleNamespace
     from mamba_clip_amd import train
     from mamba_clip_amd.data import synthetic_batch
@@ -69,8 +66,7 @@ def main():
     bad = [{"block_bytes": buf[3 * i], "side": "high" if buf[3 * i + 1] >> 32 else "low",
             "first_bad_word": buf[3 * i + 1] & 0xFFFFFFFF, "base": hex(buf[3 * i + 2])} for i in range(min(n, 64))]
     same = [all(torch.equal(a, b) for a, b in zip(finals[0], f)) for f in finals[1:]]
-    print(json.dumps({"violations": n, "first": bad[:16], "runs_equal_to_first": same,
-                      "side_tower": model.side_tower}), flush=True)
+    print(json.dumps({"violations": n, "first": bad[:16], "runs_equal_to_first": same}), flush=True)
 
 
 if __name__ == "__main__":
