@@ -33,9 +33,12 @@
 //    --siglip switch prepares logit_scale = log 10 and logit_bias = -10 for and then drops
 //    (pipeline.py:213-216), on the logits of ClipModel.get_logits (model.py:1047-1063):
 //    z = scale * X Y^T + bias, loss = coef * sum softplus(-y z) with y = +1 on the label diagonal
-//    and -1 elsewhere.  Forward: kEpi 4 reduces each tile to one partial, sum_partials_kernel
-//    folds them.  Gradient: kEpi 5 writes coef * (sigmoid(z) - [label]) through the GEMM's store
+//    and -1 elsewhere.  Forward: kEpiSigmoidLoss reduces each tile to one partial, sum_partials_kernel
+//    folds them.  Gradient: kEpiSigmoidGrad writes coef * (sigmoid(z) - [label]) through the GEMM's store
 //    epilogue and reduces the logit_scale / logit_bias gradients per tile.  No atomics.
+// Every fused entry point runs gemm_nt_kernel with one of six epilogues (kEpiStore .. kEpiSigmoidGrad);
+// launch_tile, the one place that names an instance, builds only the 41 the entry points can reach
+// (65 kernels in this file).
 #include <algorithm>
 
 #include "mc_common.h"
@@ -51,6 +54,15 @@ constexpr int kRowBytes = 64;            // one K slice of a tile row
 constexpr int kLdsStride = 80;           // padded row (bytes): conflict-free 16-lane fragment reads
 constexpr int kTileBytes = BM * kLdsStride;
 
+// gemm_nt_kernel's epilogues (its kEpi argument).  Plain ints: the value is part of every instance's
+// mangled name.
+constexpr int kEpiStore = 0;         // C = alpha * sa * sb * A B^T
+constexpr int kEpiCeStats = 1;       // fused CE forward: LSE partials and target logits
+constexpr int kEpiCeGrad = 2;        // fused CE gradient block
+constexpr int kEpiRankCount = 3;     // retrieval ranks: greater / equal counts against the targets
+constexpr int kEpiSigmoidLoss = 4;   // pairwise sigmoid loss: one partial sum per tile
+constexpr int kEpiSigmoidGrad = 5;   // pairwise sigmoid gradient block
+
 struct GemmArgs {
   int M, N, K;
   const void* A; int64_t lda;
@@ -61,21 +73,21 @@ struct GemmArgs {
   int tiles_m, tiles_n;
   int c_vec;                           // C 16-B aligned and ldc % 4 == 0: vector stores in full tiles
   int c_vec16;                         // 16-bit C: ldc % 8 == 0 as well (16-B stores of 8 values)
-  // fused cross-entropy epilogues (kEpi 1 = statistics, 2 = gradient).  Labels:
+  // fused cross-entropy epilogues (kEpiCeStats, kEpiCeGrad).  Labels:
   // row i's target column is i + off_r, column j's target row is j + off_c.
   int off_r, off_c;
   float coef_r, coef_c;
-  const float* lse_r; const float* lse_c;   // kEpi 2 inputs; NULL drops that term
-  const float* gout_dev;                    // kEpi 2 upstream scalar (NULL = 1)
-  int g_times_alpha;                        // kEpi 2: store alpha * G (then G @ Y is dX directly)
-  float2* rpart; float2* cpart;             // kEpi 1: (max, sumexp) partials [tiles_n][M], [tiles_m][N]
-  float* tgt_r; float* tgt_c;               // kEpi 1: target logits (written by the tile holding them)
-  float* gpart;                             // kEpi 2: per-workgroup sum(G * S), nullable
-  uint32_t* rcnt; uint32_t* ccnt;           // kEpi 3: packed (greater | equal << 16) counts [tiles_n][M], [tiles_m][N]
-  // pairwise sigmoid loss (kEpi 4 = forward, 5 = gradient): z = logit + beta, label column i + off_r,
-  // weight coef_r.  kEpi 4 writes its tile sum to gpart; kEpi 5 sum(g * logit) to gpart and sum(g) to bpart.
+  const float* lse_r; const float* lse_c;   // CeGrad inputs; NULL drops that term
+  const float* gout_dev;                    // CeGrad / SigmoidGrad upstream scalar (NULL = 1)
+  int g_times_alpha;                        // CeGrad / SigmoidGrad: store alpha * G (then G @ Y is dX directly)
+  float2* rpart; float2* cpart;             // CeStats: (max, sumexp) partials [tiles_n][M], [tiles_m][N]
+  float* tgt_r; float* tgt_c;               // CeStats: target logits (written by the tile holding them); RankCount input
+  float* gpart;                             // CeGrad: per-workgroup sum(G * S), nullable
+  uint32_t* rcnt; uint32_t* ccnt;           // RankCount: packed (greater | equal << 16) counts [tiles_n][M], [tiles_m][N]
+  // pairwise sigmoid loss (kEpiSigmoidLoss, kEpiSigmoidGrad): z = logit + beta, label column i + off_r,
+  // weight coef_r.  SigmoidLoss writes its tile sum to gpart; SigmoidGrad sum(g * logit) to gpart and sum(g) to bpart.
   float beta; const float* beta_dev;
-  float* bpart;                             // kEpi 5: per-workgroup sum(G), nullable with gpart
+  float* bpart;                             // SigmoidGrad: per-workgroup sum(G), nullable with gpart
 };
 
 typedef uint8_t fp8_t;   // OCP e4m3fn bits
@@ -369,10 +381,11 @@ __device__ __forceinline__ void sigmoid_loss_epilogue(const GemmArgs& g, const f
   if (tid == 0) g.gpart[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// kEpi 0: C = alpha * sa * sb * A B^T.  kEpi 1 / 2: the same tile feeds a fused
-// softmax cross-entropy epilogue instead (statistics / gradient, see below).
-// kEpi 3: the rank-count epilogue above; the K loop is the one kEpi 1 runs.
-// kEpi 4 / 5: the pairwise sigmoid loss (forward sum / gradient block), same K loop again.
+// kEpiStore (0): C = alpha * sa * sb * A B^T.  kEpiCeStats (1) / kEpiCeGrad (2): the same tile feeds a
+// fused softmax cross-entropy epilogue instead (statistics / gradient, see below).
+// kEpiRankCount (3): the rank-count epilogue above; the K loop is the one kEpiCeStats runs.
+// kEpiSigmoidLoss (4) / kEpiSigmoidGrad (5): the pairwise sigmoid loss (forward sum / gradient block),
+// same K loop again.
 template <typename TIn, typename TOut, bool kAligned, int kEpi>
 __global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmArgs g) {
   constexpr int E = (int)sizeof(TIn);
@@ -450,9 +463,9 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmArgs g) {
 
   // gradient epilogue inputs, also loaded before the K loop
   float lr[4][4], lcol[4], gout = 1.f, beta = 0.f;
-  if constexpr (kEpi == 4 || kEpi == 5) beta = g.beta_dev ? *g.beta_dev : g.beta;
-  if constexpr (kEpi == 5) gout = g.gout_dev ? *g.gout_dev : 1.f;
-  if constexpr (kEpi == 2) {
+  if constexpr (kEpi == kEpiSigmoidLoss || kEpi == kEpiSigmoidGrad) beta = g.beta_dev ? *g.beta_dev : g.beta;
+  if constexpr (kEpi == kEpiSigmoidGrad) gout = g.gout_dev ? *g.gout_dev : 1.f;
+  if constexpr (kEpi == kEpiCeGrad) {
     gout = g.gout_dev ? *g.gout_dev : 1.f;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -505,7 +518,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmArgs g) {
         af[i] = *reinterpret_cast<const uint4*>(la + (wr * 64 + i * 16 + (lane & 15)) * kLdsStride + (lane >> 4) * 16);
         bf[i] = *reinterpret_cast<const uint4*>(lb + (wc * 64 + i * 16 + (lane & 15)) * kLdsStride + (lane >> 4) * 16);
       }
-      if constexpr (kEpi != 0) {
+      if constexpr (kEpi != kEpiStore) {
         // The CE epilogues hold their logits to the fp32 lse tolerance (1e-5 absolute at |logit| ~ 20).
         // v_mfma_f32_16x16x32_fp8_fp8 does not add real-valued products as an exact fp32 sum (measured:
         // up to 2.5e-5 sum_k |a b|, 4e-4 on such a logit), so these instances feed the same bytes,
@@ -561,26 +574,26 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmArgs g) {
   // Accumulator map (16x16 MFMA C/D): acc[i][j][r] is row wr*64 + i*16 + 4*(lane>>4) + r,
   // column wc*64 + j*16 + (lane & 15) of the tile.
   const int row_base = m0 + wr * 64 + 4 * (lane >> 4), col_base = n0 + wc * 64 + (lane & 15);
-  if constexpr (kEpi == 1) {
+  if constexpr (kEpi == kEpiCeStats) {
     ce_stats_epilogue(g, acc, row_scale, col_scale, alpha, row_base, col_base, lds, tm, tn, m0, n0);
     return;
   }
-  if constexpr (kEpi == 3) {
+  if constexpr (kEpi == kEpiRankCount) {
     rank_count_epilogue(g, acc, row_scale, col_scale, alpha, row_base, col_base, lds, tm, tn, m0, n0);
     return;
   }
-  if constexpr (kEpi == 4) {
+  if constexpr (kEpi == kEpiSigmoidLoss) {
     sigmoid_loss_epilogue(g, acc, row_scale, col_scale, alpha, beta, row_base, col_base, lds);
     return;
   }
-  if constexpr (kEpi == 0) {
+  if constexpr (kEpi == kEpiStore) {
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j)
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[i][j][r] = (acc[i][j][r] * row_scale[i][r]) * (alpha * col_scale[j]);
-  } else if constexpr (kEpi == 5) {
+  } else if constexpr (kEpi == kEpiSigmoidGrad) {
     // G = gmul * coef (sigmoid(z) - [label]), z = logit + beta.  With e = exp(-|z|) and s = 1 / (1 + e):
     // sigmoid(|z|) = s and sigmoid(-|z|) = e s, so the label's sigmoid(z) - 1 = -sigmoid(-z) is formed
     // without cancellation.  The tile also sums g * logit (logit_scale gradient before the division by
@@ -1216,22 +1229,41 @@ using namespace mc;
 using namespace mc::ctr;
 
 namespace {
+// The one launcher of gemm_nt_kernel.  It instantiates what the entry points admit and nothing else:
+//  * bf16 / fp32 operands, 16-B aligned rows or not, for every epilogue;
+//  * fp8 operands for kEpiStore / kEpiCeStats / kEpiCeGrad only (mc_retrieval_ranks and the sigmoid entry
+//    points reject fp8 before fill_operands), and only kAligned: fill_operands rejects unaligned fp8 rows;
+//  * a bf16 TOut only where the epilogue stores C or G (kEpiStore, kEpiCeGrad, kEpiSigmoidGrad); the others
+//    never touch C and are always asked for fp32.
+// in_dtype has passed fill_operands and out_dtype the caller's own check (mc_gemm_nt: out_dtype, the gradient
+// entry points: g_dtype, the rest a literal MC_DTYPE_F32), so no other combination can arrive; one that did
+// would be an error here, not a launch of some neighbouring instance.
 template <int kEpi>
-void launch_gemm(const GemmArgs& g, int in_dtype, int out_dtype, bool aligned, hipStream_t s) {
+int launch_tile(const GemmArgs& g, int in_dtype, int out_dtype, bool aligned, hipStream_t s) {
+  constexpr bool kFp8In = kEpi == kEpiStore || kEpi == kEpiCeStats || kEpi == kEpiCeGrad;
+  constexpr bool kStoresC = kEpi == kEpiStore || kEpi == kEpiCeGrad || kEpi == kEpiSigmoidGrad;
+  const bool fp8 = in_dtype == MC_DTYPE_FP8_E4M3;
+  MC_CHECK((in_dtype == MC_DTYPE_BF16 || in_dtype == MC_DTYPE_F32 || (kFp8In && fp8 && aligned)) &&
+               (out_dtype == MC_DTYPE_F32 || (kStoresC && out_dtype == MC_DTYPE_BF16)),
+           MC_ERR_DTYPE, "gemm_nt_kernel: no instance for epilogue %d, in_dtype %d, out_dtype %d, aligned %d", kEpi,
+           in_dtype, out_dtype, (int)aligned);
   const dim3 grid(g.tiles_m * g.tiles_n), block(256);
-#define MC_GEMM(TI, TO)                                                                         \
-  do {                                                                                          \
-    if (aligned) hipLaunchKernelGGL((gemm_nt_kernel<TI, TO, true, kEpi>), grid, block, 0, s, g); \
-    else hipLaunchKernelGGL((gemm_nt_kernel<TI, TO, false, kEpi>), grid, block, 0, s, g);       \
-  } while (0)
-  if (in_dtype == MC_DTYPE_BF16) {
-    if (out_dtype == MC_DTYPE_F32) MC_GEMM(bf16_t, float); else MC_GEMM(bf16_t, bf16_t);
-  } else if (in_dtype == MC_DTYPE_FP8_E4M3) {
-    if (out_dtype == MC_DTYPE_F32) MC_GEMM(fp8_t, float); else MC_GEMM(fp8_t, bf16_t);
-  } else {
-    if (out_dtype == MC_DTYPE_F32) MC_GEMM(float, float); else MC_GEMM(float, bf16_t);
-  }
-#undef MC_GEMM
+  auto launch = [&](auto in, auto out) {   // the arguments only carry TIn and TOut
+    using TIn = decltype(in);
+    using TOut = decltype(out);
+    if (aligned) hipLaunchKernelGGL((gemm_nt_kernel<TIn, TOut, true, kEpi>), grid, block, 0, s, g);
+    else if constexpr (sizeof(TIn) > 1) hipLaunchKernelGGL((gemm_nt_kernel<TIn, TOut, false, kEpi>), grid, block, 0, s, g);
+  };
+  auto launch_in = [&](auto in) {
+    if constexpr (kStoresC) {
+      if (out_dtype == MC_DTYPE_BF16) return launch(in, bf16_t{});
+    }
+    launch(in, float{});
+  };
+  if (in_dtype == MC_DTYPE_BF16) launch_in(bf16_t{});
+  else if (in_dtype == MC_DTYPE_F32) launch_in(float{});
+  else if constexpr (kFp8In) launch_in(fp8_t{});
+  return MC_OK;
 }
 
 // The panel kernel's eligibility: K % 64 == 0, K <= 512; whole 16-B output vectors (N % 8, ldc % 8 and a
@@ -1288,6 +1320,27 @@ int fill_operands(GemmArgs& g, const char* who, int M, int N, int K, int in_dtyp
              "%s: fp8 operands need K, lda, ldb multiples of 16 and 16-B aligned rows", who);
   return MC_OK;
 }
+
+// C (or a G block) as the store epilogue sees it
+void bind_output(GemmArgs& g, void* C, int64_t ldc) {
+  g.C = C; g.ldc = ldc;
+  g.c_vec = aligned16(C) && ldc % 4 == 0;
+  g.c_vec16 = g.c_vec && ldc % 8 == 0;
+}
+
+// label diagonals are compared as int col - row differences in the epilogues
+inline bool label_off_ok(int64_t off) { return off > -(1 << 30) && off < (1 << 30); }
+
+int check_workspace(const char* who, const void* ws, size_t have, size_t need) {
+  MC_CHECK(ws && aligned16(ws) && have >= need, MC_ERR_WORKSPACE, "%s: workspace must be >= %zu bytes, 16-B aligned",
+           who, need);
+  return MC_OK;
+}
+
+// out[0] = coef * (part[0] + .. + part[n - 1]) / *divisor  (divisor NULL = 1)
+void fold_partials(const float* part, int n, float coef, const float* divisor, float* out, hipStream_t s) {
+  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, part, n, coef, divisor, out);
+}
 }  // namespace
 
 extern "C" int32_t mc_gemm_nt_kernel(const mc_gemm_nt_params* p) {
@@ -1312,13 +1365,10 @@ extern "C" int mc_gemm_nt(const mc_gemm_nt_params* p, void* stream) {
   MC_CHECK(p->C, MC_ERR_INVALID, "mc_gemm_nt: null C");
   GemmArgs g;
   bool aligned;
-  const int rc = fill_operands(g, "mc_gemm_nt", p->M, p->N, p->K, p->in_dtype, p->A, p->lda, p->B, p->ldb, aligned);
-  if (rc != MC_OK) return rc;
-  g.C = p->C; g.ldc = p->ldc;
+  MC_TRY(fill_operands(g, "mc_gemm_nt", p->M, p->N, p->K, p->in_dtype, p->A, p->lda, p->B, p->ldb, aligned));
+  bind_output(g, p->C, p->ldc);
   g.alpha = p->alpha; g.alpha_dev = p->alpha_dev;
   g.sa = p->row_scale_a; g.sb = p->row_scale_b;
-  g.c_vec = aligned16(p->C) && p->ldc % 4 == 0;
-  g.c_vec16 = g.c_vec && p->ldc % 8 == 0;
   if (p->in_dtype == MC_DTYPE_FP8_E4M3 && sim8_panel_ok(g, p)) {   // the C5 similarity path (K <= 512)
     launch_sim8_panel(g, p->out_dtype, (hipStream_t)stream);
   } else if (p->in_dtype == MC_DTYPE_FP8_E4M3 && p->K % kSBK == 0 && p->K > 0) {   // fp8, longer K
@@ -1326,11 +1376,9 @@ extern "C" int mc_gemm_nt(const mc_gemm_nt_params* p, void* stream) {
     if (p->out_dtype == MC_DTYPE_F32) hipLaunchKernelGGL(sim_fp8_kernel<float>, grid, block, 0, (hipStream_t)stream, g);
     else hipLaunchKernelGGL(sim_fp8_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, g);
   } else {
-    launch_gemm<0>(g, p->in_dtype, p->out_dtype, aligned, (hipStream_t)stream);
+    MC_TRY(launch_tile<kEpiStore>(g, p->in_dtype, p->out_dtype, aligned, (hipStream_t)stream));
   }
-  const hipError_t e = hipGetLastError();
-  MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "mc_gemm_nt: launch failed: %s", hipGetErrorString(e));
-  return MC_OK;
+  return check_launch("mc_gemm_nt");
 }
 
 extern "C" int mc_quant_rows_fp8(int32_t rows, int32_t cols, int32_t in_dtype, const void* X, int64_t ldx, uint8_t* Q,
@@ -1354,14 +1402,13 @@ extern "C" int mc_quant_rows_fp8(int32_t rows, int32_t cols, int32_t in_dtype, c
                        reinterpret_cast<const f16_t*>(X), ldx, Q, ldq, inv_scale);
   else
     MC_CHECK(false, MC_ERR_DTYPE, "mc_quant_rows_fp8: input must be fp32, bf16 or f16");
-  const hipError_t e = hipGetLastError();
-  MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "mc_quant_rows_fp8: launch failed: %s", hipGetErrorString(e));
-  return MC_OK;
+  return check_launch("mc_quant_rows_fp8");
 }
 
 // ------------------------------------------------------------------ fused logits + CE
 namespace {
 inline size_t al16(size_t b) { return (b + 15) & ~(size_t)15; }
+inline size_t tile_count(int M, int N) { return (size_t)((M + BM - 1) / BM) * ((N + BN - 1) / BN); }
 
 struct FusedWs {
   float2* rpart; float2* cpart; float* tgt_r; float* tgt_c; float* partial;
@@ -1383,17 +1430,49 @@ FusedWs fused_fwd_ws(int M, int N, bool cols, void* base) {
   return w;
 }
 
-int fused_common(const mc_ce_fused_params* p, const char* who, GemmArgs& g, bool& aligned) {
-  MC_CHECK(p != nullptr, MC_ERR_INVALID, "%s: null params", who);
-  const int rc = fill_operands(g, who, p->M, p->N, p->K, p->in_dtype, p->X, p->ldx, p->Y, p->ldy, aligned);
-  if (rc != MC_OK) return rc;
-  MC_CHECK(p->row_off > -(1 << 30) && p->row_off < (1 << 30) && p->col_off > -(1 << 30) && p->col_off < (1 << 30),
-           MC_ERR_SHAPE, "%s: label offsets out of range", who);
+// operands, labels and weights of a cross-entropy problem: the fields mc_ce_fused_params and
+// mc_retrieval_params share (p checked non-null by the caller)
+template <typename P>
+int ce_common(const P* p, const char* who, GemmArgs& g, bool& aligned) {
+  MC_TRY(fill_operands(g, who, p->M, p->N, p->K, p->in_dtype, p->X, p->ldx, p->Y, p->ldy, aligned));
+  MC_CHECK(label_off_ok(p->row_off) && label_off_ok(p->col_off), MC_ERR_SHAPE, "%s: label offsets out of range", who);
   g.alpha = p->scale; g.alpha_dev = p->scale_dev;
   g.sa = p->row_scale_x; g.sb = p->row_scale_y;
   g.off_r = (int)p->row_off; g.off_c = (int)p->col_off;
   g.coef_r = p->coef_r; g.coef_c = p->coef_c;
   return MC_OK;
+}
+
+// The statistics sweep of mc_ce_fused_fwd, which is also the first sweep of mc_retrieval_ranks: the tiles
+// write LSE partials and target logits into w, ce_fused_reduce_kernel folds them into lse_r / lse_c (NULL =
+// no column term) and one loss partial per block, sum_partials_kernel adds those.  g keeps the workspace
+// pointers: the rank-count sweep reads the targets through them.
+int ce_stats_sweep(GemmArgs& g, const FusedWs& w, int in_dtype, bool aligned, float* lse_r, float* lse_c,
+                   float* loss_out, hipStream_t s) {
+  g.rpart = w.rpart; g.cpart = w.cpart; g.tgt_r = w.tgt_r; g.tgt_c = w.tgt_c;
+  MC_TRY(launch_tile<kEpiCeStats>(g, in_dtype, MC_DTYPE_F32, aligned, s));
+  const int nbr = (g.M + 255) / 256, nb = nbr + (lse_c ? (g.N + 255) / 256 : 0);
+  hipLaunchKernelGGL(ce_fused_reduce_kernel, dim3(nb), dim3(256), 0, s, g.M, g.N, g.tiles_m, g.tiles_n, w.rpart,
+                     w.cpart, w.tgt_r, w.tgt_c, g.off_r, g.off_c, g.coef_r, g.coef_c, lse_r, lse_c, nbr, w.partial);
+  fold_partials(w.partial, nb, 1.f, nullptr, loss_out, s);
+  return MC_OK;
+}
+
+// The G block of a gradient entry point (mc_ce_fused_params and mc_sigmoid_loss_params name it alike)
+template <typename P>
+int bind_grad_block(const P* p, const char* who, GemmArgs& g) {
+  MC_CHECK(p->G, MC_ERR_INVALID, "%s: null G", who);
+  MC_CHECK(p->g_dtype == MC_DTYPE_F32 || p->g_dtype == MC_DTYPE_BF16, MC_ERR_DTYPE, "%s: G must be fp32 or bf16", who);
+  MC_CHECK(p->ldg >= p->N, MC_ERR_SHAPE, "%s: ldg < N", who);
+  g.gout_dev = p->gout_dev; g.g_times_alpha = p->g_times_scale != 0;
+  bind_output(g, p->G, p->ldg);
+  return MC_OK;
+}
+
+// the logit_scale gradient: *dscale_out = sum(G * logit) / scale from the per-tile sums (G there is without gmul)
+template <typename P>
+void fold_dscale(const P* p, const GemmArgs& g, hipStream_t s) {
+  fold_partials(g.gpart, g.tiles_m * g.tiles_n, p->scale_dev ? 1.f : 1.f / p->scale, p->scale_dev, p->dscale_out, s);
 }
 }  // namespace
 
@@ -1403,59 +1482,40 @@ extern "C" size_t mc_ce_fused_fwd_workspace_bytes(int32_t M, int32_t N, int32_t 
 }
 
 extern "C" int mc_ce_fused_fwd(const mc_ce_fused_params* p, void* stream) {
+  const char* who = "mc_ce_fused_fwd";
   GemmArgs g;
   bool aligned;
-  const int rc = fused_common(p, "mc_ce_fused_fwd", g, aligned);
-  if (rc != MC_OK) return rc;
-  MC_CHECK(p->lse_r && p->loss_out, MC_ERR_INVALID, "mc_ce_fused_fwd: null lse_r / loss_out");
-  const bool cols = p->lse_c != nullptr;
-  const FusedWs w = fused_fwd_ws(p->M, p->N, cols, p->workspace);
-  MC_CHECK(p->workspace && aligned16(p->workspace) && p->workspace_bytes >= w.bytes, MC_ERR_WORKSPACE,
-           "mc_ce_fused_fwd: workspace must be >= %zu bytes, 16-B aligned", w.bytes);
-  g.rpart = w.rpart; g.cpart = w.cpart; g.tgt_r = w.tgt_r; g.tgt_c = w.tgt_c;
-  hipStream_t s = (hipStream_t)stream;
-  launch_gemm<1>(g, p->in_dtype, MC_DTYPE_F32, aligned, s);
-  const int nbr = (p->M + 255) / 256, nb = nbr + (cols ? (p->N + 255) / 256 : 0);
-  hipLaunchKernelGGL(ce_fused_reduce_kernel, dim3(nb), dim3(256), 0, s, p->M, p->N, g.tiles_m, g.tiles_n, w.rpart,
-                     w.cpart, w.tgt_r, w.tgt_c, g.off_r, g.off_c, p->coef_r, p->coef_c, p->lse_r, p->lse_c, nbr,
-                     w.partial);
-  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, w.partial, nb, 1.f, nullptr, p->loss_out);
-  const hipError_t e = hipGetLastError();
-  MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "mc_ce_fused_fwd: launch failed: %s", hipGetErrorString(e));
-  return MC_OK;
+  MC_CHECK(p != nullptr, MC_ERR_INVALID, "%s: null params", who);
+  MC_TRY(ce_common(p, who, g, aligned));
+  MC_CHECK(p->lse_r && p->loss_out, MC_ERR_INVALID, "%s: null lse_r / loss_out", who);
+  const FusedWs w = fused_fwd_ws(p->M, p->N, p->lse_c != nullptr, p->workspace);
+  MC_TRY(check_workspace(who, p->workspace, p->workspace_bytes, w.bytes));
+  MC_TRY(ce_stats_sweep(g, w, p->in_dtype, aligned, p->lse_r, p->lse_c, p->loss_out, (hipStream_t)stream));
+  return check_launch(who);
 }
 
 extern "C" size_t mc_ce_fused_grad_workspace_bytes(int32_t M, int32_t N) {
   if (M <= 0 || N <= 0) return 0;
-  return al16((size_t)((M + BM - 1) / BM) * ((N + BN - 1) / BN) * sizeof(float));
+  return al16(tile_count(M, N) * sizeof(float));
 }
 
 extern "C" int mc_ce_fused_grad(const mc_ce_fused_params* p, void* stream) {
+  const char* who = "mc_ce_fused_grad";
   GemmArgs g;
   bool aligned;
-  const int rc = fused_common(p, "mc_ce_fused_grad", g, aligned);
-  if (rc != MC_OK) return rc;
-  MC_CHECK(p->lse_r || p->lse_c, MC_ERR_INVALID, "mc_ce_fused_grad: lse_r and lse_c both NULL");
-  MC_CHECK(p->G, MC_ERR_INVALID, "mc_ce_fused_grad: null G");
-  MC_CHECK(p->g_dtype == MC_DTYPE_F32 || p->g_dtype == MC_DTYPE_BF16, MC_ERR_DTYPE,
-           "mc_ce_fused_grad: G must be fp32 or bf16");
-  MC_CHECK(p->ldg >= p->N, MC_ERR_SHAPE, "mc_ce_fused_grad: ldg < N");
-  const size_t need = mc_ce_fused_grad_workspace_bytes(p->M, p->N);
-  MC_CHECK(!p->dscale_out || (p->workspace && aligned16(p->workspace) && p->workspace_bytes >= need),
-           MC_ERR_WORKSPACE, "mc_ce_fused_grad: workspace must be >= %zu bytes, 16-B aligned", need);
-  g.lse_r = p->lse_r; g.lse_c = p->lse_c; g.gout_dev = p->gout_dev; g.g_times_alpha = p->g_times_scale != 0;
-  g.C = p->G; g.ldc = p->ldg;
-  g.c_vec = aligned16(p->G) && p->ldg % 4 == 0;
-  g.c_vec16 = g.c_vec && p->ldg % 8 == 0;
-  g.gpart = p->dscale_out ? reinterpret_cast<float*>(p->workspace) : nullptr;
+  MC_CHECK(p != nullptr, MC_ERR_INVALID, "%s: null params", who);
+  MC_TRY(ce_common(p, who, g, aligned));
+  MC_CHECK(p->lse_r || p->lse_c, MC_ERR_INVALID, "%s: lse_r and lse_c both NULL", who);
+  MC_TRY(bind_grad_block(p, who, g));
+  if (p->dscale_out) {   // the workspace holds the per-tile sums of G S and is needed only for them
+    MC_TRY(check_workspace(who, p->workspace, p->workspace_bytes, mc_ce_fused_grad_workspace_bytes(p->M, p->N)));
+    g.gpart = reinterpret_cast<float*>(p->workspace);
+  }
+  g.lse_r = p->lse_r; g.lse_c = p->lse_c;
   hipStream_t s = (hipStream_t)stream;
-  launch_gemm<2>(g, p->in_dtype, p->g_dtype, aligned, s);
-  if (p->dscale_out)   // sum(G S) / scale: the scale gradient (G here is without gmul)
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, g.gpart, g.tiles_m * g.tiles_n,
-                       p->scale_dev ? 1.f : 1.f / p->scale, p->scale_dev, p->dscale_out);
-  const hipError_t e = hipGetLastError();
-  MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "mc_ce_fused_grad: launch failed: %s", hipGetErrorString(e));
-  return MC_OK;
+  MC_TRY(launch_tile<kEpiCeGrad>(g, p->in_dtype, p->g_dtype, aligned, s));
+  if (p->dscale_out) fold_dscale(p, g, s);
+  return check_launch(who);
 }
 
 // ------------------------------------------------------------------ retrieval ranks (evaluation)
@@ -1492,138 +1552,80 @@ extern "C" int mc_retrieval_ranks(const mc_retrieval_params* p, void* stream) {
            "%s: inputs must be bf16 or fp32", who);
   GemmArgs g;
   bool aligned;
-  const int rc = fill_operands(g, who, p->M, p->N, p->K, p->in_dtype, p->X, p->ldx, p->Y, p->ldy, aligned);
-  if (rc != MC_OK) return rc;
-  MC_CHECK(p->row_off > -(1 << 30) && p->row_off < (1 << 30) && p->col_off > -(1 << 30) && p->col_off < (1 << 30),
-           MC_ERR_SHAPE, "%s: label offsets out of range", who);
+  MC_TRY(ce_common(p, who, g, aligned));
   MC_CHECK(p->gt_r && p->eq_r && p->gt_c && p->eq_c && p->lse_r && p->lse_c && p->loss_out, MC_ERR_INVALID,
            "%s: null output", who);
   const RankWs w = rank_ws(p->M, p->N, p->workspace);
-  MC_CHECK(p->workspace && aligned16(p->workspace) && p->workspace_bytes >= w.bytes, MC_ERR_WORKSPACE,
-           "%s: workspace must be >= %zu bytes, 16-B aligned", who, w.bytes);
-  g.alpha = p->scale; g.alpha_dev = p->scale_dev;
-  g.sa = p->row_scale_x; g.sb = p->row_scale_y;
-  g.off_r = (int)p->row_off; g.off_c = (int)p->col_off;
-  g.coef_r = p->coef_r; g.coef_c = p->coef_c;
-  g.rpart = w.f.rpart; g.cpart = w.f.cpart; g.tgt_r = w.f.tgt_r; g.tgt_c = w.f.tgt_c;
-  g.rcnt = w.rcnt; g.ccnt = w.ccnt;
+  MC_TRY(check_workspace(who, p->workspace, p->workspace_bytes, w.bytes));
   hipStream_t s = (hipStream_t)stream;
-  // sweep 1: statistics + target logits (exactly mc_ce_fused_fwd)
-  launch_gemm<1>(g, p->in_dtype, MC_DTYPE_F32, aligned, s);
-  const int nbr = (p->M + 255) / 256, nb = nbr + (p->N + 255) / 256;
-  hipLaunchKernelGGL(ce_fused_reduce_kernel, dim3(nb), dim3(256), 0, s, p->M, p->N, g.tiles_m, g.tiles_n, w.f.rpart,
-                     w.f.cpart, w.f.tgt_r, w.f.tgt_c, g.off_r, g.off_c, p->coef_r, p->coef_c, p->lse_r, p->lse_c, nbr,
-                     w.f.partial);
-  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, w.f.partial, nb, 1.f, nullptr, p->loss_out);
+  // sweep 1: statistics + target logits
+  MC_TRY(ce_stats_sweep(g, w.f, p->in_dtype, aligned, p->lse_r, p->lse_c, p->loss_out, s));
   // sweep 2: the same tiles against the recorded targets, then the fold
-  const dim3 grid(g.tiles_m * g.tiles_n), block(256);
-  if (p->in_dtype == MC_DTYPE_BF16) {
-    if (aligned) hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, float, true, 3>), grid, block, 0, s, g);
-    else hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, float, false, 3>), grid, block, 0, s, g);
-  } else {
-    if (aligned) hipLaunchKernelGGL((gemm_nt_kernel<float, float, true, 3>), grid, block, 0, s, g);
-    else hipLaunchKernelGGL((gemm_nt_kernel<float, float, false, 3>), grid, block, 0, s, g);
-  }
+  g.rcnt = w.rcnt; g.ccnt = w.ccnt;
+  MC_TRY(launch_tile<kEpiRankCount>(g, p->in_dtype, MC_DTYPE_F32, aligned, s));
   const int nf = (int)(((int64_t)p->M + p->N + 255) / 256);
   hipLaunchKernelGGL(rank_fold_kernel, dim3(nf), dim3(256), 0, s, p->M, p->N, g.tiles_m, g.tiles_n, w.rcnt, w.ccnt,
                      g.off_r, g.off_c, p->gt_r, p->eq_r, p->gt_c, p->eq_c);
-  const hipError_t e = hipGetLastError();
-  MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e));
-  return MC_OK;
+  return check_launch(who);
 }
 
 // ------------------------------------------------------------------ pairwise sigmoid loss (SigLIP)
 namespace {
-inline size_t sigmoid_tiles(int M, int N) { return (size_t)((M + BM - 1) / BM) * ((N + BN - 1) / BN); }
-
 int sigmoid_common(const mc_sigmoid_loss_params* p, const char* who, GemmArgs& g, bool& aligned) {
   MC_CHECK(p != nullptr, MC_ERR_INVALID, "%s: null params", who);
   MC_CHECK(p->in_dtype == MC_DTYPE_BF16 || p->in_dtype == MC_DTYPE_F32, MC_ERR_DTYPE,
            "%s: inputs must be bf16 or fp32", who);
   MC_CHECK(p->K > 0, MC_ERR_SHAPE, "%s: bad shape", who);
-  const int rc = fill_operands(g, who, p->M, p->N, p->K, p->in_dtype, p->X, p->ldx, p->Y, p->ldy, aligned);
-  if (rc != MC_OK) return rc;
-  MC_CHECK(p->row_off > -(1 << 30) && p->row_off < (1 << 30), MC_ERR_SHAPE, "%s: label offset out of range", who);
+  MC_TRY(fill_operands(g, who, p->M, p->N, p->K, p->in_dtype, p->X, p->ldx, p->Y, p->ldy, aligned));
+  MC_CHECK(label_off_ok(p->row_off), MC_ERR_SHAPE, "%s: label offset out of range", who);
   g.alpha = p->scale; g.alpha_dev = p->scale_dev;
   g.beta = p->bias; g.beta_dev = p->bias_dev;
   g.off_r = (int)p->row_off;
   g.coef_r = p->coef;
   return MC_OK;
 }
-
-template <typename TOut, int kEpi>
-void launch_sigmoid(const GemmArgs& g, int in_dtype, bool aligned, hipStream_t s) {
-  const dim3 grid(g.tiles_m * g.tiles_n), block(256);
-  if (in_dtype == MC_DTYPE_BF16) {
-    if (aligned) hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, TOut, true, kEpi>), grid, block, 0, s, g);
-    else hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, TOut, false, kEpi>), grid, block, 0, s, g);
-  } else {
-    if (aligned) hipLaunchKernelGGL((gemm_nt_kernel<float, TOut, true, kEpi>), grid, block, 0, s, g);
-    else hipLaunchKernelGGL((gemm_nt_kernel<float, TOut, false, kEpi>), grid, block, 0, s, g);
-  }
-}
 }  // namespace
 
 extern "C" size_t mc_sigmoid_loss_fwd_workspace_bytes(int32_t M, int32_t N) {
   if (M <= 0 || N <= 0) return 0;
-  return al16(sigmoid_tiles(M, N) * sizeof(float));
+  return al16(tile_count(M, N) * sizeof(float));
 }
 
 extern "C" int mc_sigmoid_loss_fwd(const mc_sigmoid_loss_params* p, void* stream) {
   const char* who = "mc_sigmoid_loss_fwd";
   GemmArgs g;
   bool aligned;
-  const int rc = sigmoid_common(p, who, g, aligned);
-  if (rc != MC_OK) return rc;
+  MC_TRY(sigmoid_common(p, who, g, aligned));
   MC_CHECK(p->loss_out, MC_ERR_INVALID, "%s: null loss_out", who);
-  const size_t need = mc_sigmoid_loss_fwd_workspace_bytes(p->M, p->N);
-  MC_CHECK(p->workspace && aligned16(p->workspace) && p->workspace_bytes >= need, MC_ERR_WORKSPACE,
-           "%s: workspace must be >= %zu bytes, 16-B aligned", who, need);
+  MC_TRY(check_workspace(who, p->workspace, p->workspace_bytes, mc_sigmoid_loss_fwd_workspace_bytes(p->M, p->N)));
   g.gpart = reinterpret_cast<float*>(p->workspace);
   hipStream_t s = (hipStream_t)stream;
-  launch_sigmoid<float, 4>(g, p->in_dtype, aligned, s);
-  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, g.gpart, g.tiles_m * g.tiles_n, p->coef, nullptr,
-                     p->loss_out);
-  const hipError_t e = hipGetLastError();
-  MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e));
-  return MC_OK;
+  MC_TRY(launch_tile<kEpiSigmoidLoss>(g, p->in_dtype, MC_DTYPE_F32, aligned, s));
+  fold_partials(g.gpart, g.tiles_m * g.tiles_n, p->coef, nullptr, p->loss_out, s);
+  return check_launch(who);
 }
 
 // two partials per tile: sum(g * logit) then sum(g), each block 16-B aligned
 extern "C" size_t mc_sigmoid_loss_grad_workspace_bytes(int32_t M, int32_t N) {
   if (M <= 0 || N <= 0) return 0;
-  return 2 * al16(sigmoid_tiles(M, N) * sizeof(float));
+  return 2 * al16(tile_count(M, N) * sizeof(float));
 }
 
 extern "C" int mc_sigmoid_loss_grad(const mc_sigmoid_loss_params* p, void* stream) {
   const char* who = "mc_sigmoid_loss_grad";
   GemmArgs g;
   bool aligned;
-  const int rc = sigmoid_common(p, who, g, aligned);
-  if (rc != MC_OK) return rc;
-  MC_CHECK(p->G, MC_ERR_INVALID, "%s: null G", who);
-  MC_CHECK(p->g_dtype == MC_DTYPE_F32 || p->g_dtype == MC_DTYPE_BF16, MC_ERR_DTYPE, "%s: G must be fp32 or bf16", who);
-  MC_CHECK(p->ldg >= p->N, MC_ERR_SHAPE, "%s: ldg < N", who);
-  const bool stats = p->dscale_out || p->dbias_out;
-  const size_t need = mc_sigmoid_loss_grad_workspace_bytes(p->M, p->N);
-  MC_CHECK(!stats || (p->workspace && aligned16(p->workspace) && p->workspace_bytes >= need), MC_ERR_WORKSPACE,
-           "%s: workspace must be >= %zu bytes, 16-B aligned", who, need);
-  g.gout_dev = p->gout_dev; g.g_times_alpha = p->g_times_scale != 0;
-  g.C = p->G; g.ldc = p->ldg;
-  g.c_vec = aligned16(p->G) && p->ldg % 4 == 0;
-  g.c_vec16 = g.c_vec && p->ldg % 8 == 0;
-  g.gpart = stats ? reinterpret_cast<float*>(p->workspace) : nullptr;
-  g.bpart = stats ? reinterpret_cast<float*>(reinterpret_cast<char*>(p->workspace) + need / 2) : nullptr;
+  MC_TRY(sigmoid_common(p, who, g, aligned));
+  MC_TRY(bind_grad_block(p, who, g));
+  if (p->dscale_out || p->dbias_out) {   // the workspace holds the per-tile sums and is needed only for them
+    const size_t need = mc_sigmoid_loss_grad_workspace_bytes(p->M, p->N);
+    MC_TRY(check_workspace(who, p->workspace, p->workspace_bytes, need));
+    g.gpart = reinterpret_cast<float*>(p->workspace);
+    g.bpart = reinterpret_cast<float*>(reinterpret_cast<char*>(p->workspace) + need / 2);
+  }
   hipStream_t s = (hipStream_t)stream;
-  if (p->g_dtype == MC_DTYPE_F32) launch_sigmoid<float, 5>(g, p->in_dtype, aligned, s);
-  else launch_sigmoid<bf16_t, 5>(g, p->in_dtype, aligned, s);
-  const int tiles = g.tiles_m * g.tiles_n;
-  if (p->dscale_out)   // sum(g * logit) / scale
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, g.gpart, tiles,
-                       p->scale_dev ? 1.f : 1.f / p->scale, p->scale_dev, p->dscale_out);
-  if (p->dbias_out)
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, g.bpart, tiles, 1.f, nullptr, p->dbias_out);
-  const hipError_t e = hipGetLastError();
-  MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e));
-  return MC_OK;
+  MC_TRY(launch_tile<kEpiSigmoidGrad>(g, p->in_dtype, p->g_dtype, aligned, s));
+  if (p->dscale_out) fold_dscale(p, g, s);
+  if (p->dbias_out) fold_partials(g.bpart, g.tiles_m * g.tiles_n, 1.f, nullptr, p->dbias_out, s);
+  return check_launch(who);
 }

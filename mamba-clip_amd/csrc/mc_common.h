@@ -7,6 +7,8 @@
 #include <stdio.h>
 #include <string>
 
+#include "../../include/mc_scan.h"   // MC_OK / MC_ERR_*
+
 namespace mc {
 
 constexpr float kLog2e = 1.4426950408889634f;
@@ -287,6 +289,20 @@ const char* last_error();
       return (code);                   \
     }                                  \
   } while (0)
+
+// pass on the error code of a helper that has already described its failure
+#define MC_TRY(call)                    \
+  do {                                  \
+    const int mc_rc_ = (call);          \
+    if (mc_rc_ != MC_OK) return mc_rc_; \
+  } while (0)
+
+// the tail of an entry point: a launch the runtime refused shows up here (launches never synchronise)
+inline int check_launch(const char* who) {
+  const hipError_t e = hipGetLastError();
+  MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e));
+  return MC_OK;
+}
 
 // Bijective blockIdx remap so that consecutive logical blocks (neighbours that
 // share operands) run on one XCD: hardware deals blocks round-robin over

@@ -1208,12 +1208,6 @@ using namespace mc::ops;
     else { using T = f16_t; __VA_ARGS__; }                          \
   } while (0)
 
-static int check_launch(const char* who) {
-  const hipError_t e = hipGetLastError();
-  MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e));
-  return MC_OK;
-}
-
 extern "C" int mc_add_rmsnorm_fwd(int32_t rows, int32_t cols, int32_t dtype, const void* x, const float* res_in,
                                   const float* w, float eps, void* y, float* res_out, float* rstd, void* stream) {
   MC_CHECK(dtype >= MC_DTYPE_F32 && dtype <= MC_DTYPE_F16, MC_ERR_DTYPE, "mc_add_rmsnorm_fwd: bad dtype");

@@ -529,12 +529,6 @@ static void reduce_partials(int s, int n, const float* src, int64_t stride, floa
 }
 
 // ------------------------------------------------------------------ host side
-static int check_launch(const char* who) {
-  const hipError_t e = hipGetLastError();
-  MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e));
-  return MC_OK;
-}
-
 static int conv_validate(const mc_ss2d_conv_params* p, const char* who) {
   MC_CHECK(p != nullptr, MC_ERR_INVALID, "%s: null params", who);
   MC_CHECK(p->batch >= 0 && p->height >= 0 && p->width >= 0 && p->channels >= 0, MC_ERR_SHAPE, "%s: negative shape", who);

@@ -134,14 +134,48 @@ def clip_loss_fp8(image_features, text_features, logit_scale):
 CE_GRAD_BLOCK_ELEMS = 1 << 24
 
 
-def _ce_params(X, Y, sc, row_off, coef_r, col_off, coef_c, sx=None, sy=None):
-    p = _lib.CEFusedParams()
+def _fused_operands(X, Y):
+    """X, Y as the fused kernels read them: bf16 / fp32 kept, any other dtype to fp32, contiguous."""
+    dt = X.dtype if X.dtype in (torch.bfloat16, torch.float32) else torch.float32
+    return X.to(dt).contiguous(), Y.to(dt).contiguous()
+
+
+def _fill_operands(p, X, Y):
+    """The problem fields the CE, retrieval and sigmoid parameter structs share."""
     p.M, p.K = X.shape
     p.N = Y.shape[0]
     p.in_dtype = _lib.dtype_code(X.dtype)
     p.X, p.ldx, p.Y, p.ldy = X.data_ptr(), X.stride(0), Y.data_ptr(), Y.stride(0)
+    return p
+
+
+def _set_scalar(p, name, v):
+    """p.<name>_dev for a 0-d fp32 device tensor (read on the device: no host sync), p.<name> for a python float."""
+    if torch.is_tensor(v):
+        setattr(p, name + "_dev", v.data_ptr())
+    else:
+        setattr(p, name, float(v))
+
+
+def _bind_ws(p, nbytes, device):
+    """A workspace of nbytes bound to p; the caller holds the returned tensor until the launch is enqueued."""
+    ws = _ws(nbytes, device)
+    p.workspace, p.workspace_bytes = ws.data_ptr(), nbytes
+    return ws
+
+
+def _bind_grad_block(p, X, Y, gout, g_dtype):
+    """A fresh (M, N) G block of g_dtype bound to p: G = scale * gout * dloss/dlogits, so G @ Y is dX directly."""
+    G = torch.empty(X.shape[0], Y.shape[0], device=X.device, dtype=g_dtype)
+    p.gout_dev = gout.data_ptr()
+    p.g_dtype, p.g_times_scale, p.G, p.ldg = _lib.dtype_code(g_dtype), 1, G.data_ptr(), G.stride(0)
+    return G
+
+
+def _ce_params(X, Y, sc, row_off, coef_r, col_off, coef_c, sx=None, sy=None):
+    p = _fill_operands(_lib.CEFusedParams(), X, Y)
     p.row_scale_x, p.row_scale_y = _lib.ptr(sx), _lib.ptr(sy)
-    p.scale_dev = sc.data_ptr()
+    _set_scalar(p, "scale", sc)
     p.row_off, p.coef_r, p.col_off, p.coef_c = int(row_off), float(coef_r), int(col_off), float(coef_c)
     return p
 
@@ -160,10 +194,8 @@ def ce_fused_fwd(X, Y, sc, row_off=0, coef_r=1.0, col_off=0, coef_c=0.0, sx=None
     lse_c = torch.empty(N, device=X.device, dtype=torch.float32) if cols else None
     loss = torch.empty((), device=X.device, dtype=torch.float32)
     p = _ce_params(X, Y, sc, row_off, coef_r, col_off, coef_c, sx, sy)
-    ws_b = lib.mc_ce_fused_fwd_workspace_bytes(M, N, int(cols))
-    ws = _ws(ws_b, X.device)
     p.lse_r, p.lse_c, p.loss_out = lse_r.data_ptr(), _lib.ptr(lse_c), loss.data_ptr()
-    p.workspace, p.workspace_bytes = ws.data_ptr(), ws_b
+    ws = _bind_ws(p, lib.mc_ce_fused_fwd_workspace_bytes(M, N, int(cols)), X.device)
     _lib.check(lib.mc_ce_fused_fwd(p, _lib.stream_handle(X.device)), "mc_ce_fused_fwd")
     return loss, lse_r, lse_c
 
@@ -172,19 +204,14 @@ def ce_fused_grad(X, Y, sc, lse_r, lse_c, row_off, coef_r, col_off, coef_c, gout
     """(sc * G, dscale): one block of dloss/dS recomputed from (lse_r, lse_c), S = sc * X @ Y^T
     (mc_ce_fused_grad); ``G @ Y`` is then dX directly.  dscale is sum(G S) / sc or None."""
     lib = _lib.load()
-    M, N = X.shape[0], Y.shape[0]
-    G = torch.empty(M, N, device=X.device, dtype=g_dtype)
     p = _ce_params(X, Y, sc, row_off, coef_r, col_off, coef_c)
     p.lse_r, p.lse_c = _lib.ptr(lse_r), _lib.ptr(lse_c)
-    p.gout_dev = gout.data_ptr()
-    p.g_dtype, p.g_times_scale, p.G, p.ldg = _lib.dtype_code(g_dtype), 1, G.data_ptr(), N
-    dscale = None
-    ws = None
+    G = _bind_grad_block(p, X, Y, gout, g_dtype)
+    dscale = ws = None
     if want_dscale:
         dscale = torch.empty((), device=X.device, dtype=torch.float32)
-        ws_b = lib.mc_ce_fused_grad_workspace_bytes(M, N)
-        ws = _ws(ws_b, X.device)
-        p.dscale_out, p.workspace, p.workspace_bytes = dscale.data_ptr(), ws.data_ptr(), ws_b
+        p.dscale_out = dscale.data_ptr()
+        ws = _bind_ws(p, lib.mc_ce_fused_grad_workspace_bytes(p.M, p.N), X.device)
     _lib.check(lib.mc_ce_fused_grad(p, _lib.stream_handle(X.device)), "mc_ce_fused_grad")
     return G, dscale
 
@@ -255,22 +282,14 @@ def retrieval_ranks(X, Y, scale, row_off=0, col_off=0):
     lse = torch.empty(M + N, device=dev, dtype=torch.float32)
     lse_r, lse_c = lse[:M], lse[M:]
     loss = torch.empty((), device=dev, dtype=torch.float32)
-    p = _lib.RetrievalParams()
-    p.M, p.N, p.K = M, N, X.shape[1]
-    p.in_dtype = _lib.dtype_code(X.dtype)
-    p.X, p.ldx, p.Y, p.ldy = X.data_ptr(), X.stride(0), Y.data_ptr(), Y.stride(0)
-    sc = None
+    p = _fill_operands(_lib.RetrievalParams(), X, Y)
     if torch.is_tensor(scale):
-        sc = scale.detach().reshape(()).to(device=dev, dtype=torch.float32).contiguous()
-        p.scale_dev = sc.data_ptr()
-    else:
-        p.scale = float(scale)
+        scale = scale.detach().reshape(()).to(device=dev, dtype=torch.float32).contiguous()
+    _set_scalar(p, "scale", scale)
     p.row_off, p.coef_r, p.col_off, p.coef_c = int(row_off), 0.5 / M, int(col_off), 0.5 / N
     p.gt_r, p.eq_r, p.gt_c, p.eq_c = gt_r.data_ptr(), eq_r.data_ptr(), gt_c.data_ptr(), eq_c.data_ptr()
     p.lse_r, p.lse_c, p.loss_out = lse_r.data_ptr(), lse_c.data_ptr(), loss.data_ptr()
-    ws_b = lib.mc_retrieval_ranks_workspace_bytes(M, N)
-    ws = _ws(ws_b, dev)
-    p.workspace, p.workspace_bytes = ws.data_ptr(), ws_b
+    ws = _bind_ws(p, lib.mc_retrieval_ranks_workspace_bytes(M, N), dev)
     _lib.check(lib.mc_retrieval_ranks(p, _lib.stream_handle(dev)), "mc_retrieval_ranks")
     return RetrievalRanks(gt_r, eq_r, gt_c, eq_c, lse_r, lse_c, loss)
 
@@ -289,6 +308,44 @@ def _block_rows(other):
     return max(128, CE_GRAD_BLOCK_ELEMS // max(other, 1) // 128 * 128)
 
 
+def _blocked_backward(Xc, Yc, xdt, ydt, want_dx, want_dy, want_stats, row_block, col_block):
+    """(dX, dY, stats) of a fused loss of S = scale * Xc @ Yc^T without S or dS in memory.
+
+    ``row_block(r0, r1)`` returns ``(G, *scalars)``: rows r0:r1 of scale * dloss/dS in the operands'
+    dtype and that block's share of every scalar gradient (ignored unless ``want_stats``);
+    ``col_block(c0, c1)`` the same for rows c0:c1 of the transposed problem.  dX = G @ Y goes row
+    block by row block and dY = G^T @ X column block by column block, each block at most
+    CE_GRAD_BLOCK_ELEMS elements; both products are NT GEMMs against a K-contiguous transpose
+    (fp32: a copy for mc_gemm_nt; bf16: a view torch.mm reads as it is).  ``stats`` holds each scalar
+    summed over the row blocks, None unless wanted.  dX / dY come back in xdt / ydt."""
+    M, N = Xc.shape[0], Yc.shape[0]
+    dX = dY = stats = None
+    Yt = Yc.t().contiguous() if Yc.dtype == torch.float32 else Yc.t()
+    Xt = Xc.t().contiguous() if Xc.dtype == torch.float32 else Xc.t()
+    if want_dx or want_stats:
+        dX = torch.empty_like(Xc) if want_dx else None
+        R = _block_rows(N)
+        parts = []
+        for r0 in range(0, M, R):
+            r1 = min(M, r0 + R)
+            G, *scalars = row_block(r0, r1)
+            if dX is not None:
+                _mm_nt(G, Yt, dX[r0:r1])
+            parts.append(scalars)
+        if want_stats:
+            stats = [p[0] if len(p) == 1 else torch.stack(p).sum() for p in zip(*parts)]
+        dX = dX.to(xdt) if dX is not None else None
+    if want_dy:
+        dY = torch.empty_like(Yc)
+        R = _block_rows(M)
+        for c0 in range(0, N, R):
+            c1 = min(N, c0 + R)
+            GT, *_ = col_block(c0, c1)
+            _mm_nt(GT, Xt, dY[c0:c1])
+        dY = dY.to(ydt)
+    return dX, dY, stats
+
+
 class ScaledLogitsCE(torch.autograd.Function):
     """loss = coef_r * sum_i CE_row_i(S) + coef_c * sum_j CE_col_j(S),  S = scale * X @ Y^T.
 
@@ -298,19 +355,15 @@ class ScaledLogitsCE(torch.autograd.Function):
     inputs the exact-fp32 MFMA path; logits and statistics are fp32.
 
     Neither pass stores S.  Forward: mc_ce_fused_fwd (logit tiles reduced to
-    LSE partials in registers).  Backward: dX in row blocks -- G_blk (recomputed
-    by mc_ce_fused_grad, already times scale) @ Y -- and dY in column blocks
-    from the transposed problem (roles of X/Y, rows/columns, offsets and
-    coefficients swapped) -- G^T_blk @ X; both products are plain NN GEMMs
-    (hipBLASLt), so no operand is ever transposed in memory.  Blocks hold at
-    most CE_GRAD_BLOCK_ELEMS elements.
+    LSE partials in registers).  Backward (_blocked_backward): dX in row blocks
+    -- G_blk (recomputed by mc_ce_fused_grad, already times scale) @ Y -- and dY
+    in column blocks from the transposed problem (roles of X/Y, rows/columns,
+    offsets and coefficients swapped) -- G^T_blk @ X.
     """
 
     @staticmethod
     def forward(ctx, X, Y, scale, row_off, coef_r, col_off, coef_c):
-        dt = X.dtype if X.dtype in (torch.bfloat16, torch.float32) else torch.float32
-        Xc = X.to(dt).contiguous()
-        Yc = Y.to(dt).contiguous()
+        Xc, Yc = _fused_operands(X, Y)
         sc = scale.reshape(()).float().contiguous()
         loss, lse_r, lse_c = ce_fused_fwd(Xc, Yc, sc, row_off, coef_r, col_off, coef_c)
         ctx.save_for_backward(Xc, Yc, sc, lse_r, lse_c if lse_c is not None else lse_r)
@@ -324,38 +377,20 @@ class ScaledLogitsCE(torch.autograd.Function):
         lse_c = lse_c if has_c else None
         gout = gout.reshape(()).float().contiguous()
         gdt = Xc.dtype  # G feeds the GEMMs in the operands' dtype
-        M, N = Xc.shape[0], Yc.shape[0]
         want_ds = ctx.needs_input_grad[2]
-        dX = dY = dscale = None
-        # second operands of dX = G @ Y and dY = G^T @ X as (K-contiguous) row-major transposes
-        Yt = Yc.t().contiguous() if Yc.dtype == torch.float32 else Yc.t()
-        Xt = Xc.t().contiguous() if Xc.dtype == torch.float32 else Xc.t()
-        if ctx.needs_input_grad[0] or want_ds:
-            dX = torch.empty_like(Xc) if ctx.needs_input_grad[0] else None
-            R = _block_rows(N)
-            parts = []
-            for r0 in range(0, M, R):
-                r1 = min(M, r0 + R)
-                G, ds = ce_fused_grad(Xc[r0:r1], Yc, sc, lse_r[r0:r1], lse_c, row_off + r0, coef_r, col_off - r0,
-                                      coef_c, gout, gdt, want_ds)
-                if dX is not None:
-                    _mm_nt(G, Yt, dX[r0:r1])
-                if ds is not None:
-                    parts.append(ds)
-            if want_ds:
-                dscale = parts[0] if len(parts) == 1 else torch.stack(parts).sum()
-            dX = dX.to(xdt) if dX is not None else None
-        if ctx.needs_input_grad[1]:
-            dY = torch.empty_like(Yc)
-            R = _block_rows(M)
-            for c0 in range(0, N, R):
-                c1 = min(N, c0 + R)
-                # transposed problem: rows = columns c0..c1 of S, columns = rows of S
-                GT, _ = ce_fused_grad(Yc[c0:c1], Xc, sc, lse_c[c0:c1] if has_c else None, lse_r, col_off + c0,
-                                      coef_c, row_off - c0, coef_r, gout, gdt)
-                _mm_nt(GT, Xt, dY[c0:c1])
-            dY = dY.to(ydt)
-        dS = dscale.to(sdt).reshape(sshape) if want_ds else None
+
+        def row_block(r0, r1):
+            return ce_fused_grad(Xc[r0:r1], Yc, sc, lse_r[r0:r1], lse_c, row_off + r0, coef_r, col_off - r0, coef_c,
+                                 gout, gdt, want_ds)
+
+        def col_block(c0, c1):
+            # transposed problem: rows = columns c0..c1 of S, columns = rows of S
+            return ce_fused_grad(Yc[c0:c1], Xc, sc, lse_c[c0:c1] if has_c else None, lse_r, col_off + c0, coef_c,
+                                 row_off - c0, coef_r, gout, gdt)
+
+        dX, dY, stats = _blocked_backward(Xc, Yc, xdt, ydt, ctx.needs_input_grad[0], ctx.needs_input_grad[1], want_ds,
+                                          row_block, col_block)
+        dS = stats[0].to(sdt).reshape(sshape) if want_ds else None
         return dX, dY, dS, None, None, None, None
 
 
@@ -365,19 +400,9 @@ def scaled_logits_ce(X, Y, scale, row_off=0, coef_r=1.0, col_off=0, coef_c=0.0):
 
 def _sigmoid_params(X, Y, sc, bs, row_off, coef):
     """sc / bs: a 0-d fp32 device tensor (read on the device) or a python float."""
-    p = _lib.SigmoidLossParams()
-    p.M, p.K = X.shape
-    p.N = Y.shape[0]
-    p.in_dtype = _lib.dtype_code(X.dtype)
-    p.X, p.ldx, p.Y, p.ldy = X.data_ptr(), X.stride(0), Y.data_ptr(), Y.stride(0)
-    if torch.is_tensor(sc):
-        p.scale_dev = sc.data_ptr()
-    else:
-        p.scale = float(sc)
-    if torch.is_tensor(bs):
-        p.bias_dev = bs.data_ptr()
-    else:
-        p.bias = float(bs)
+    p = _fill_operands(_lib.SigmoidLossParams(), X, Y)
+    _set_scalar(p, "scale", sc)
+    _set_scalar(p, "bias", bs)
     p.row_off, p.coef = int(row_off), float(coef)
     return p
 
@@ -386,12 +411,10 @@ def sigmoid_loss_fwd(X, Y, sc, bs, row_off=0, coef=1.0):
     """coef * sum_ij softplus(-y_ij z_ij), z = sc * X @ Y^T + bs, y = +1 where j == i + row_off else -1,
     tile-wise on the matrix cores without storing z (mc_sigmoid_loss_fwd).  A 0-d fp32 device scalar."""
     lib = _lib.load()
-    M, N = X.shape[0], Y.shape[0]
     loss = torch.empty((), device=X.device, dtype=torch.float32)
     p = _sigmoid_params(X, Y, sc, bs, row_off, coef)
-    ws_b = lib.mc_sigmoid_loss_fwd_workspace_bytes(M, N)
-    ws = _ws(ws_b, X.device)
-    p.loss_out, p.workspace, p.workspace_bytes = loss.data_ptr(), ws.data_ptr(), ws_b
+    p.loss_out = loss.data_ptr()
+    ws = _bind_ws(p, lib.mc_sigmoid_loss_fwd_workspace_bytes(p.M, p.N), X.device)
     _lib.check(lib.mc_sigmoid_loss_fwd(p, _lib.stream_handle(X.device)), "mc_sigmoid_loss_fwd")
     return loss
 
@@ -400,19 +423,14 @@ def sigmoid_loss_grad(X, Y, sc, bs, row_off, coef, gout, g_dtype, want_stats=Fal
     """(sc * G, dscale, dbias): one block of gout * dloss/dz recomputed from the features
     (mc_sigmoid_loss_grad); ``G @ Y`` is then dX directly.  dscale / dbias are None unless asked for."""
     lib = _lib.load()
-    M, N = X.shape[0], Y.shape[0]
-    G = torch.empty(M, N, device=X.device, dtype=g_dtype)
     p = _sigmoid_params(X, Y, sc, bs, row_off, coef)
-    p.gout_dev = gout.data_ptr()
-    p.g_dtype, p.g_times_scale, p.G, p.ldg = _lib.dtype_code(g_dtype), 1, G.data_ptr(), N
+    G = _bind_grad_block(p, X, Y, gout, g_dtype)
     dscale = dbias = ws = None
     if want_stats:
         stats = torch.empty(2, device=X.device, dtype=torch.float32)
         dscale, dbias = stats[0], stats[1]
-        ws_b = lib.mc_sigmoid_loss_grad_workspace_bytes(M, N)
-        ws = _ws(ws_b, X.device)
         p.dscale_out, p.dbias_out = dscale.data_ptr(), dbias.data_ptr()
-        p.workspace, p.workspace_bytes = ws.data_ptr(), ws_b
+        ws = _bind_ws(p, lib.mc_sigmoid_loss_grad_workspace_bytes(p.M, p.N), X.device)
     _lib.check(lib.mc_sigmoid_loss_grad(p, _lib.stream_handle(X.device)), "mc_sigmoid_loss_grad")
     return G, dscale, dbias
 
@@ -422,17 +440,15 @@ class SigmoidLogitsLoss(torch.autograd.Function):
     j == i + row_off and -1 elsewhere: the pairwise sigmoid (SigLIP) loss.
 
     Neither pass stores z.  Forward: mc_sigmoid_loss_fwd (tiles reduced to one partial each).
-    Backward, as in ScaledLogitsCE: dX in row blocks -- G_blk (recomputed by mc_sigmoid_loss_grad,
-    already times scale) @ Y -- and dY in column blocks from the transposed problem (roles of X / Y
-    swapped, label offset negated) -- G^T_blk @ X.  Blocks hold at most CE_GRAD_BLOCK_ELEMS elements.
-    The scale and bias gradients are summed over the row blocks of the X pass only.
+    Backward (_blocked_backward, as in ScaledLogitsCE): dX in row blocks -- G_blk (recomputed by
+    mc_sigmoid_loss_grad, already times scale) @ Y -- and dY in column blocks from the transposed
+    problem (roles of X / Y swapped, label offset negated) -- G^T_blk @ X.  The scale and bias
+    gradients are summed over the row blocks of the X pass only.
     """
 
     @staticmethod
     def forward(ctx, X, Y, scale, bias, row_off, coef):
-        dt = X.dtype if X.dtype in (torch.bfloat16, torch.float32) else torch.float32
-        Xc = X.to(dt).contiguous()
-        Yc = Y.to(dt).contiguous()
+        Xc, Yc = _fused_operands(X, Y)
         s_t, b_t = torch.is_tensor(scale), torch.is_tensor(bias)
         sc = scale.reshape(()).to(device=Xc.device, dtype=torch.float32).contiguous() if s_t else float(scale)
         bs = bias.reshape(()).to(device=Xc.device, dtype=torch.float32).contiguous() if b_t else float(bias)
@@ -454,42 +470,22 @@ class SigmoidLogitsLoss(torch.autograd.Function):
             bs = rest.pop(0)
         gout = gout.reshape(()).float().contiguous()
         gdt = Xc.dtype  # G feeds the GEMMs in the operands' dtype
-        M, N = Xc.shape[0], Yc.shape[0]
         want_ds = smeta is not None and ctx.needs_input_grad[2]
         want_db = bmeta is not None and ctx.needs_input_grad[3]
         want_stats = want_ds or want_db
-        dX = dY = dscale = dbias = None
-        # second operands of dX = G @ Y and dY = G^T @ X as (K-contiguous) row-major transposes
-        Yt = Yc.t().contiguous() if Yc.dtype == torch.float32 else Yc.t()
-        Xt = Xc.t().contiguous() if Xc.dtype == torch.float32 else Xc.t()
-        if ctx.needs_input_grad[0] or want_stats:
-            dX = torch.empty_like(Xc) if ctx.needs_input_grad[0] else None
-            R = _block_rows(N)
-            ds_parts, db_parts = [], []
-            for r0 in range(0, M, R):
-                r1 = min(M, r0 + R)
-                G, ds, db = sigmoid_loss_grad(Xc[r0:r1], Yc, sc, bs, row_off + r0, coef, gout, gdt, want_stats)
-                if dX is not None:
-                    _mm_nt(G, Yt, dX[r0:r1])
-                if want_stats:
-                    ds_parts.append(ds)
-                    db_parts.append(db)
-            if want_stats:
-                dscale = ds_parts[0] if len(ds_parts) == 1 else torch.stack(ds_parts).sum()
-                dbias = db_parts[0] if len(db_parts) == 1 else torch.stack(db_parts).sum()
-            dX = dX.to(xdt) if dX is not None else None
-        if ctx.needs_input_grad[1]:
-            dY = torch.empty_like(Yc)
-            R = _block_rows(M)
-            for c0 in range(0, N, R):
-                c1 = min(N, c0 + R)
-                # transposed problem: rows = columns c0..c1 of z, columns = rows of z; z's label
-                # j == i + row_off reads i == (j - c0) + (c0 - row_off) there
-                GT, _, _ = sigmoid_loss_grad(Yc[c0:c1], Xc, sc, bs, c0 - row_off, coef, gout, gdt)
-                _mm_nt(GT, Xt, dY[c0:c1])
-            dY = dY.to(ydt)
-        dS = dscale.to(smeta[0]).reshape(smeta[1]) if want_ds else None
-        dB = dbias.to(bmeta[0]).reshape(bmeta[1]) if want_db else None
+
+        def row_block(r0, r1):
+            return sigmoid_loss_grad(Xc[r0:r1], Yc, sc, bs, row_off + r0, coef, gout, gdt, want_stats)
+
+        def col_block(c0, c1):
+            # transposed problem: rows = columns c0..c1 of z, columns = rows of z; z's label
+            # j == i + row_off reads i == (j - c0) + (c0 - row_off) there
+            return sigmoid_loss_grad(Yc[c0:c1], Xc, sc, bs, c0 - row_off, coef, gout, gdt)
+
+        dX, dY, stats = _blocked_backward(Xc, Yc, xdt, ydt, ctx.needs_input_grad[0], ctx.needs_input_grad[1],
+                                          want_stats, row_block, col_block)
+        dS = stats[0].to(smeta[0]).reshape(smeta[1]) if want_ds else None
+        dB = stats[1].to(bmeta[0]).reshape(bmeta[1]) if want_db else None
         return dX, dY, dS, dB, None, None
 
 

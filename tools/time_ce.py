@@ -1,6 +1,7 @@
-"""Time the fused logits+CE (mc_ce_fused_*), forward and forward + backward, at a given N, E.
+"""Time the fused losses, forward and forward + backward, at a given N, E: the logits + CE
+(mc_ce_fused_*) and, with --siglip, the pairwise sigmoid loss (mc_sigmoid_loss_*) on the same operands.
 
-    python tools/time_ce.py --n 8192 --e 512 [--fp8]
+    python tools/time_ce.py --n 8192 --e 512 [--fp8] [--siglip]
 """
 import argparse
 import os
@@ -9,7 +10,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mamba-clip_amd"))
-from mamba_clip_amd.ops import clip_loss_fp8, scaled_logits_ce  # noqa: E402
+from mamba_clip_amd.ops import clip_loss_fp8, scaled_logits_ce, sigmoid_logits_loss  # noqa: E402
 
 
 def timed(fn, iters=20, warm=5):
@@ -30,6 +31,7 @@ def main():
     ap.add_argument("--n", type=int, default=8192)
     ap.add_argument("--e", type=int, default=512)
     ap.add_argument("--fp8", action="store_true")
+    ap.add_argument("--siglip", action="store_true")
     a = ap.parse_args()
     g = torch.Generator(device="cuda").manual_seed(0)
     X = torch.nn.functional.normalize(torch.randn(a.n, a.e, device="cuda", generator=g), dim=-1).bfloat16()
@@ -57,6 +59,26 @@ def main():
     if a.fp8:
         t8 = timed(lambda: clip_loss_fp8(X, Y, sc))
         print(f"N={a.n} E={a.e} fp8 fused loss (incl. quantisation): {t8:.3f} ms")
+    if a.siglip:
+        # SigLIP's initial point (logit_scale = 10, logit_bias = -10), both learnable device scalars
+        sl, bl = torch.tensor(10.0, device="cuda"), torch.tensor(-10.0, device="cuda")
+        slg, blg = sl.clone().requires_grad_(True), bl.clone().requires_grad_(True)
+
+        def siglip():
+            sigmoid_logits_loss(Xg, Yg, slg, blg, 0, 1.0 / a.n).backward()
+
+        def siglip_fwd():
+            with torch.no_grad():
+                sigmoid_logits_loss(X, Y, sl, bl, 0, 1.0 / a.n)
+
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        b0 = torch.cuda.memory_allocated()
+        t_s = timed(siglip)
+        pk_s = torch.cuda.max_memory_allocated() - b0
+        t_sf = timed(siglip_fwd)
+        print(f"N={a.n} E={a.e} bf16 siglip: fused fwd {t_sf:.3f} ms ({flop / t_sf / 1e9:.0f} TFLOP/s on the logits "
+              f"GEMM), fused fwd+bwd {t_s:.3f} ms (peak +{pk_s / 2**20:.0f} MiB)")
 
 
 if __name__ == "__main__":
