@@ -9,6 +9,7 @@
 #include "../../include/mc_ops.h"
 
 namespace mc {
+
 namespace ops {
 
 // ------------------------------------------------------------------ RMSNorm
@@ -34,6 +35,30 @@ __device__ __forceinline__ void st_f32v(float* __restrict__ p, const float (&v)[
     *reinterpret_cast<float4*>(p + e4) = make_float4(v[e4], v[e4 + 1], v[e4 + 2], v[e4 + 3]);
 }
 
+// The 4 waves of a block add their per-lane partials in a fixed order, ((wave 0 + 1) + 2) + 3, through
+// __shared__ float red[3][64 * V] of the caller.  fold_stage: waves 1 .. 3 stage acc, then the barrier; every wave
+// of the block must call it.  fold_sum: element e of the sum, for a lane of wave 0 holding a = acc[e].
+template <int V>
+__device__ __forceinline__ void fold_stage(float (&red)[3][64 * V], const float (&acc)[V], int lane) {
+  const int w = threadIdx.x >> 6;
+  if (w > 0) {
+#pragma unroll
+    for (int e = 0; e < V; ++e) red[w - 1][lane * V + e] = acc[e];
+  }
+  __syncthreads();
+}
+template <int V>
+__device__ __forceinline__ float fold_sum(const float (&red)[3][64 * V], float a, int lane, int e) {
+  return ((a + red[0][lane * V + e]) + red[1][lane * V + e]) + red[2][lane * V + e];
+}
+
+// rows [r0, r1) of the block's row slice: slice blockIdx.y of gridDim.y equal ones
+__device__ __forceinline__ void slice_range(int rows, int& r0, int& r1) {
+  const int per = (rows + gridDim.y - 1) / gridDim.y;
+  r0 = blockIdx.y * per;
+  r1 = min(rows, r0 + per);
+}
+
 // Sum over the 64 lanes, the same bits in every lane: an xor butterfly on VALU only (DPP inside
 // 16-lane rows, permlane swaps across rows) instead of six ds_bpermute round trips.
 __device__ __forceinline__ float wave_allsum(float v) {
@@ -51,6 +76,31 @@ __device__ __forceinline__ float wave_allsum(float v) {
   return __uint_as_float(p32[0]) + __uint_as_float(p32[1]);                                       // lane ^ 32
 }
 
+// The row walk of the wave-per-row kernels: the body runs for i = 0 .. NV - 1 with v = lane + 64 * i, the lane's
+// vectors of the row, those past its end (v >= nvec) skipped.  Expands in place, fully unrolled; NV, lane and
+// nvec are the enclosing kernel's.
+#define MC_FOR_EACH_VEC(i, v)                    \
+  _Pragma("unroll") for (int i = 0; i < NV; ++i) \
+    if (const int v = lane + 64 * i; v < nvec)
+
+// RMSNorm's row arithmetic, one 16-B vector at a time (the row walk is the caller's):
+//   forward   ss = sum h^2, rstd = rsqrt(ss / cols + eps), y = h * rstd * w
+//   backward  g = dy * w, dot = sum g * h, c = dot * rstd^2 / cols, dh = rstd * (g - h * c)
+template <int V>
+__device__ __forceinline__ void rms_sumsq(const float (&h)[V], float& ss) {
+#pragma unroll
+  for (int e = 0; e < V; ++e) ss = fmaf(h[e], h[e], ss);
+}
+__device__ __forceinline__ float rms_rstd(float ss, int cols, float eps) { return rsqrtf(ss / cols + eps); }
+__device__ __forceinline__ float rms_y(float h, float rs, float w) { return h * rs * w; }
+__device__ __forceinline__ float rms_bwd_g(float dy, float w, float h, float& dot) {
+  const float g = dy * w;
+  dot = fmaf(g, h, dot);
+  return g;
+}
+__device__ __forceinline__ float rms_bwd_c(float dot, float rs, int cols) { return dot * rs * rs / cols; }
+__device__ __forceinline__ float rms_bwd_dh(float g, float h, float rs, float c) { return rs * (g - h * c); }
+
 template <typename T, int NV>
 __global__ __launch_bounds__(256) void add_rmsnorm_fwd_kernel(int rows, int cols, const T* __restrict__ x,
                                                               const float* __restrict__ res_in,
@@ -63,11 +113,7 @@ __global__ __launch_bounds__(256) void add_rmsnorm_fwd_kernel(int rows, int cols
   const int nwaves = (gridDim.x * blockDim.x) >> 6;
   const int nvec = cols / V;
   float wr[NV][V];
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int v = lane + 64 * i;
-    if (v < nvec) ld_f32v<V>(w + v * V, wr[i]);
-  }
+  MC_FOR_EACH_VEC(i, v) ld_f32v<V>(w + v * V, wr[i]);
   // the NEXT row's x / res_in in flight during this row's math (rows <= 1024 wide)
   uint4 qx[NV];
   float qr[NV][V];
@@ -97,30 +143,21 @@ __global__ __launch_bounds__(256) void add_rmsnorm_fwd_kernel(int rows, int cols
     }
     float h[NV][V];
     float ss = 0.f;
+    MC_FOR_EACH_VEC(i, v) {
 #pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int v = lane + 64 * i;
-      if (v < nvec) {
-#pragma unroll
-        for (int e = 0; e < V; ++e) h[i][e] = elem_f<T>(qx[i], e) + qr[i][e];
-#pragma unroll
-        for (int e = 0; e < V; ++e) ss = fmaf(h[i][e], h[i][e], ss);
-      }
+      for (int e = 0; e < V; ++e) h[i][e] = elem_f<T>(qx[i], e) + qr[i][e];
+      rms_sumsq<V>(h[i], ss);
     }
     ss = wave_allsum(ss);
-    const float rs = rsqrtf(ss / cols + eps);
+    const float rs = rms_rstd(ss, cols, eps);
     if (lane == 0) rstd[row] = rs;
+    MC_FOR_EACH_VEC(i, v) {
+      const int64_t off = (int64_t)row * cols + v * V;
+      float o[V];
 #pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int v = lane + 64 * i;
-      if (v < nvec) {
-        const int64_t off = (int64_t)row * cols + v * V;
-        float o[V];
-#pragma unroll
-        for (int e = 0; e < V; ++e) o[e] = h[i][e] * rs * wr[i][e];
-        st16(y + off, pack_f<T>(o));
-        if (res_out) st_f32v<V>(res_out + off, h[i]);
-      }
+      for (int e = 0; e < V; ++e) o[e] = rms_y(h[i][e], rs, wr[i][e]);
+      st16(y + off, pack_f<T>(o));
+      if (res_out) st_f32v<V>(res_out + off, h[i]);
     }
     if constexpr (kPrefetch) {
 #pragma unroll
@@ -133,9 +170,10 @@ __global__ __launch_bounds__(256) void add_rmsnorm_fwd_kernel(int rows, int cols
   }
 }
 
-// The 4 waves of a block fold their per-lane column partials in LDS in a fixed order (wave 0 + 1 + 2 + 3)
-// and wave 0 writes ONE partial row per block: the column-sum passes then read kNormGrid rows, not
-// 4 kNormGrid.  Every wave of the block must call it (it holds two barriers per vector).
+// The 4 waves of a block fold their per-lane column partials (fold_sum's order) and wave 0 writes ONE partial row
+// per block: the column-sum passes then read kNormGrid rows, not 4 kNormGrid.  Every wave of the block must call it
+// (two barriers per vector: the second frees the staging for the next vector).  The staging is fold_stage's,
+// written out: through the call, four add_layernorm_bwd_kernel instances compile to other address arithmetic.
 template <int NV, int V>
 __device__ __forceinline__ void block_fold_store(const float (&acc)[NV][V], int lane, int nvec, float* __restrict__ dst) {
   __shared__ float red[3][64 * V];
@@ -151,7 +189,7 @@ __device__ __forceinline__ void block_fold_store(const float (&acc)[NV][V], int 
     if (w == 0 && v < nvec) {
       float o[V];
 #pragma unroll
-      for (int e = 0; e < V; ++e) o[e] = ((acc[i][e] + red[0][lane * V + e]) + red[1][lane * V + e]) + red[2][lane * V + e];
+      for (int e = 0; e < V; ++e) o[e] = fold_sum<V>(red, acc[i][e], lane, e);
       st_f32v<V>(dst + v * V, o);
     }
     __syncthreads();
@@ -183,40 +221,31 @@ __global__ __launch_bounds__(256) void add_rmsnorm_bwd_kernel(int rows, int cols
     const float rs = rstd[row];
     float h[NV][V], g[NV][V];
     float dot = 0.f;
+    MC_FOR_EACH_VEC(i, v) {
+      const int64_t off = (int64_t)row * cols + v * V;
+      const uint4 q = ld16(dy + off);
+      ld_f32v<V>(hbuf + off, h[i]);
 #pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int v = lane + 64 * i;
-      if (v < nvec) {
-        const int64_t off = (int64_t)row * cols + v * V;
-        const uint4 q = ld16(dy + off);
-        ld_f32v<V>(hbuf + off, h[i]);
-#pragma unroll
-        for (int e = 0; e < V; ++e) {
-          const float d = elem_f<T>(q, e);
-          g[i][e] = d * wr[i][e];
-          dot = fmaf(g[i][e], h[i][e], dot);
-          dwacc[i][e] = fmaf(d, h[i][e] * rs, dwacc[i][e]);
-        }
+      for (int e = 0; e < V; ++e) {
+        const float d = elem_f<T>(q, e);
+        g[i][e] = rms_bwd_g(d, wr[i][e], h[i][e], dot);
+        dwacc[i][e] = fmaf(d, h[i][e] * rs, dwacc[i][e]);
       }
     }
     dot = wave_allsum(dot);
-    const float c = dot * rs * rs / cols;
+    const float c = rms_bwd_c(dot, rs, cols);
+    MC_FOR_EACH_VEC(i, v) {
+      const int64_t off = (int64_t)row * cols + v * V;
+      float o[V];
+      float r[V];
+      if (dres) ld_f32v<V>(dres + off, r);
 #pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int v = lane + 64 * i;
-      if (v < nvec) {
-        const int64_t off = (int64_t)row * cols + v * V;
-        float o[V];
-        float r[V];
-        if (dres) ld_f32v<V>(dres + off, r);
-#pragma unroll
-        for (int e = 0; e < V; ++e) {
-          o[e] = rs * (g[i][e] - h[i][e] * c);
-          if (dres) o[e] += r[e];
-        }
-        if (dx) st16(dx + off, pack_f<T>(o));
-        if (dres_in) st_f32v<V>(dres_in + off, o);
+      for (int e = 0; e < V; ++e) {
+        o[e] = rms_bwd_dh(g[i][e], h[i][e], rs, c);
+        if (dres) o[e] += r[e];
       }
+      if (dx) st16(dx + off, pack_f<T>(o));
+      if (dres_in) st_f32v<V>(dres_in + off, o);
     }
   }
   block_fold_store<NV, V>(dwacc, lane, nvec, dw_part + (int64_t)blockIdx.x * cols);
@@ -225,7 +254,7 @@ __global__ __launch_bounds__(256) void add_rmsnorm_bwd_kernel(int rows, int cols
 // ------------------------------------------------------------------ last-token add + RMSNorm
 // The Mamba text tower's final norm on the pooled row only: one workgroup per caption finds the
 // last position whose token is not pad_id (all 64 bits compared; 0 when the whole row is pad) and
-// its wave 0 normalises that one row of x (+ res_in) with add_rmsnorm_fwd_kernel's arithmetic.
+// its wave 0 normalises that one row of x (+ res_in), through the helpers add_rmsnorm_fwd_kernel calls.
 template <typename T, int NV>
 __global__ __launch_bounds__(256) void last_token_rmsnorm_fwd_kernel(int T_, int Lp, int cols,
                                                                      const int64_t* __restrict__ tokens, int64_t pad_id,
@@ -253,40 +282,31 @@ __global__ __launch_bounds__(256) void last_token_rmsnorm_fwd_kernel(int T_, int
   const int64_t src = ((int64_t)b * Lp + p) * cols, dst = (int64_t)b * cols;
   float h[NV][V], wr[NV][V];
   float ss = 0.f;
+  MC_FOR_EACH_VEC(i, v) {
+    ld_f32v<V>(w + v * V, wr[i]);
+    const uint4 q = ld16(x + src + v * V);
+    float r[V];
 #pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int v = lane + 64 * i;
-    if (v < nvec) {
-      ld_f32v<V>(w + v * V, wr[i]);
-      const uint4 q = ld16(x + src + v * V);
-      float r[V];
+    for (int e = 0; e < V; ++e) r[e] = 0.f;
+    if (res_in) ld_f32v<V>(res_in + src + v * V, r);
 #pragma unroll
-      for (int e = 0; e < V; ++e) r[e] = 0.f;
-      if (res_in) ld_f32v<V>(res_in + src + v * V, r);
-#pragma unroll
-      for (int e = 0; e < V; ++e) h[i][e] = elem_f<T>(q, e) + r[e];
-#pragma unroll
-      for (int e = 0; e < V; ++e) ss = fmaf(h[i][e], h[i][e], ss);
-    }
+    for (int e = 0; e < V; ++e) h[i][e] = elem_f<T>(q, e) + r[e];
+    rms_sumsq<V>(h[i], ss);
   }
   ss = wave_allsum(ss);
-  const float rs = rsqrtf(ss / cols + eps);
+  const float rs = rms_rstd(ss, cols, eps);
   if (lane == 0) rstd[b] = rs;
+  MC_FOR_EACH_VEC(i, v) {
+    float o[V];
 #pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int v = lane + 64 * i;
-    if (v < nvec) {
-      float o[V];
-#pragma unroll
-      for (int e = 0; e < V; ++e) o[e] = h[i][e] * rs * wr[i][e];
-      st16(y + dst + v * V, pack_f<T>(o));
-      st_f32v<V>(h_out + dst + v * V, h[i]);
-    }
+    for (int e = 0; e < V; ++e) o[e] = rms_y(h[i][e], rs, wr[i][e]);
+    st16(y + dst + v * V, pack_f<T>(o));
+    st_f32v<V>(h_out + dst + v * V, h[i]);
   }
 }
 
 // Backward in one launch.  Blocks [0, row_blocks): one wave per row of the (batch * Lp, cols)
-// gradients, grid-stride; row pos[b] of caption b gets add_rmsnorm_bwd_kernel's dh, every other
+// gradients, grid-stride; row pos[b] of caption b gets dh through add_rmsnorm_bwd_kernel's helpers, every other
 // row zeros (a pos outside [0, Lp) matches no row: nothing is addressed through it).  Blocks from
 // row_blocks on: dw, one thread per 16-B vector of columns, the captions added in order b = 0, 1, ...
 template <typename T, int NV>
@@ -323,11 +343,7 @@ __global__ __launch_bounds__(256) void last_token_rmsnorm_bwd_kernel(int batch, 
   const int nwaves = (row_blocks * blockDim.x) >> 6;
   const int rows = batch * Lp;
   float wr[NV][V];
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int v = lane + 64 * i;
-    if (v < nvec) ld_f32v<V>(w + v * V, wr[i]);
-  }
+  MC_FOR_EACH_VEC(i, v) ld_f32v<V>(w + v * V, wr[i]);
   for (int row = wave; row < rows; row += nwaves) {
     const int b = row / Lp;
     const int64_t out = (int64_t)row * cols;
@@ -335,45 +351,30 @@ __global__ __launch_bounds__(256) void last_token_rmsnorm_bwd_kernel(int batch, 
       float z[V];
 #pragma unroll
       for (int e = 0; e < V; ++e) z[e] = 0.f;
-#pragma unroll
-      for (int i = 0; i < NV; ++i) {
-        const int v = lane + 64 * i;
-        if (v < nvec) {
-          st16(dx + out + v * V, make_uint4(0u, 0u, 0u, 0u));
-          if (dres_in) st_f32v<V>(dres_in + out + v * V, z);
-        }
+      MC_FOR_EACH_VEC(i, v) {
+        st16(dx + out + v * V, make_uint4(0u, 0u, 0u, 0u));
+        if (dres_in) st_f32v<V>(dres_in + out + v * V, z);
       }
       continue;
     }
     const float rs = rstd[b];
     float h[NV][V], g[NV][V];
     float dot = 0.f;
+    MC_FOR_EACH_VEC(i, v) {
+      const int64_t off = (int64_t)b * cols + v * V;
+      const uint4 q = ld16(dy + off);
+      ld_f32v<V>(hbuf + off, h[i]);
 #pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int v = lane + 64 * i;
-      if (v < nvec) {
-        const int64_t off = (int64_t)b * cols + v * V;
-        const uint4 q = ld16(dy + off);
-        ld_f32v<V>(hbuf + off, h[i]);
-#pragma unroll
-        for (int e = 0; e < V; ++e) {
-          g[i][e] = elem_f<T>(q, e) * wr[i][e];
-          dot = fmaf(g[i][e], h[i][e], dot);
-        }
-      }
+      for (int e = 0; e < V; ++e) g[i][e] = rms_bwd_g(elem_f<T>(q, e), wr[i][e], h[i][e], dot);
     }
     dot = wave_allsum(dot);
-    const float c = dot * rs * rs / cols;
+    const float c = rms_bwd_c(dot, rs, cols);
+    MC_FOR_EACH_VEC(i, v) {
+      float o[V];
 #pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int v = lane + 64 * i;
-      if (v < nvec) {
-        float o[V];
-#pragma unroll
-        for (int e = 0; e < V; ++e) o[e] = rs * (g[i][e] - h[i][e] * c);
-        st16(dx + out + v * V, pack_f<T>(o));
-        if (dres_in) st_f32v<V>(dres_in + out + v * V, o);
-      }
+      for (int e = 0; e < V; ++e) o[e] = rms_bwd_dh(g[i][e], h[i][e], rs, c);
+      st16(dx + out + v * V, pack_f<T>(o));
+      if (dres_in) st_f32v<V>(dres_in + out + v * V, o);
     }
   }
 }
@@ -441,16 +442,12 @@ __global__ __launch_bounds__(256) void add_layernorm_fwd_kernel(int rows, int co
   const int nwaves = (gridDim.x * blockDim.x) >> 6;
   const int nvec = cols / V;
   float wr[NV][V], br[NV][V];
+  MC_FOR_EACH_VEC(i, v) {
+    ld_f32v<V>(w + v * V, wr[i]);
+    if (bias) ld_f32v<V>(bias + v * V, br[i]);
+    else
 #pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int v = lane + 64 * i;
-    if (v < nvec) {
-      ld_f32v<V>(w + v * V, wr[i]);
-      if (bias) ld_f32v<V>(bias + v * V, br[i]);
-      else
-#pragma unroll
-        for (int e = 0; e < V; ++e) br[i][e] = 0.f;
-    }
+      for (int e = 0; e < V; ++e) br[i][e] = 0.f;
   }
   // the NEXT row's x / res in flight during this row's math (as the backward; rows <= 1024 wide)
   uint4 qx[NV], qr[NV];
@@ -477,47 +474,35 @@ __global__ __launch_bounds__(256) void add_layernorm_fwd_kernel(int rows, int co
     }
     float h[NV][V];
     float sum = 0.f;
+    MC_FOR_EACH_VEC(i, v) {
+      const int64_t off = (int64_t)row * cols + v * V;
+      const uint4 q = qx[i];
+      if (res) {
+        const uint4 r = qr[i];
 #pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int v = lane + 64 * i;
-      if (v < nvec) {
-        const int64_t off = (int64_t)row * cols + v * V;
-        const uint4 q = qx[i];
-        if (res) {
-          const uint4 r = qr[i];
+        for (int e = 0; e < V; ++e) h[i][e] = to_f(from_f<T>(elem_f<T>(q, e) + elem_f<T>(r, e)));
+        if (h_out) st16(h_out + off, pack_f<T>(h[i]));
+      } else {
 #pragma unroll
-          for (int e = 0; e < V; ++e) h[i][e] = to_f(from_f<T>(elem_f<T>(q, e) + elem_f<T>(r, e)));
-          if (h_out) st16(h_out + off, pack_f<T>(h[i]));
-        } else {
-#pragma unroll
-          for (int e = 0; e < V; ++e) h[i][e] = elem_f<T>(q, e);
-        }
-#pragma unroll
-        for (int e = 0; e < V; ++e) sum += h[i][e];
+        for (int e = 0; e < V; ++e) h[i][e] = elem_f<T>(q, e);
       }
+#pragma unroll
+      for (int e = 0; e < V; ++e) sum += h[i][e];
     }
     sum = wave_allsum(sum);
     const float mu = sum / cols;
     float ss = 0.f;
+    MC_FOR_EACH_VEC(i, v)
 #pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int v = lane + 64 * i;
-      if (v < nvec)
-#pragma unroll
-        for (int e = 0; e < V; ++e) { const float c = h[i][e] - mu; ss = fmaf(c, c, ss); }
-    }
+      for (int e = 0; e < V; ++e) { const float c = h[i][e] - mu; ss = fmaf(c, c, ss); }
     ss = wave_allsum(ss);
     const float rs = rsqrtf(ss / cols + eps);
     if (lane == 0) { mean_out[row] = mu; rstd_out[row] = rs; }
+    MC_FOR_EACH_VEC(i, v) {
+      float o[V];
 #pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int v = lane + 64 * i;
-      if (v < nvec) {
-        float o[V];
-#pragma unroll
-        for (int e = 0; e < V; ++e) o[e] = fmaf((h[i][e] - mu) * rs, wr[i][e], br[i][e]);
-        st16(y + (int64_t)row * cols + v * V, pack_f<T>(o));
-      }
+      for (int e = 0; e < V; ++e) o[e] = fmaf((h[i][e] - mu) * rs, wr[i][e], br[i][e]);
+      st16(y + (int64_t)row * cols + v * V, pack_f<T>(o));
     }
     if constexpr (kPrefetch) {
 #pragma unroll
@@ -579,42 +564,34 @@ __global__ __launch_bounds__(256) void add_layernorm_bwd_kernel(int rows, int co
     }
     float xh[NV][V], g[NV][V];
     float sg = 0.f, sgx = 0.f;
+    MC_FOR_EACH_VEC(i, v) {
 #pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int v = lane + 64 * i;
-      if (v < nvec) {
-#pragma unroll
-        for (int e = 0; e < V; ++e) {
-          const float d = elem_f<T>(qd[i], e);
-          xh[i][e] = (elem_f<T>(qh[i], e) - mu) * rs;
-          g[i][e] = d * wr[i][e];
-          sg += g[i][e];
-          sgx = fmaf(g[i][e], xh[i][e], sgx);
-          dwacc[i][e] = fmaf(d, xh[i][e], dwacc[i][e]);
-          dbacc[i][e] += d;
-        }
+      for (int e = 0; e < V; ++e) {
+        const float d = elem_f<T>(qd[i], e);
+        xh[i][e] = (elem_f<T>(qh[i], e) - mu) * rs;
+        g[i][e] = d * wr[i][e];
+        sg += g[i][e];
+        sgx = fmaf(g[i][e], xh[i][e], sgx);
+        dwacc[i][e] = fmaf(d, xh[i][e], dwacc[i][e]);
+        dbacc[i][e] += d;
       }
     }
     sg = wave_allsum(sg);
     sgx = wave_allsum(sgx);
     const float mg = sg / cols, mgx = sgx / cols;
+    MC_FOR_EACH_VEC(i, v) {
+      const int64_t off = (int64_t)row * cols + v * V;
+      float o[V];
 #pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int v = lane + 64 * i;
-      if (v < nvec) {
-        const int64_t off = (int64_t)row * cols + v * V;
-        float o[V];
+      for (int e = 0; e < V; ++e) {
+        o[e] = rs * (g[i][e] - mg - xh[i][e] * mgx);
+        if (dh) o[e] += elem_f<T>(qr[i], e);
+      }
+      const uint4 oq = pack_f<T>(o);
+      st16(dx + off, oq);
+      if constexpr (kDxSum) {
 #pragma unroll
-        for (int e = 0; e < V; ++e) {
-          o[e] = rs * (g[i][e] - mg - xh[i][e] * mgx);
-          if (dh) o[e] += elem_f<T>(qr[i], e);
-        }
-        const uint4 oq = pack_f<T>(o);
-        st16(dx + off, oq);
-        if constexpr (kDxSum) {
-#pragma unroll
-          for (int e = 0; e < V; ++e) dxacc[i][e] += elem_f<T>(oq, e);
-        }
+        for (int e = 0; e < V; ++e) dxacc[i][e] += elem_f<T>(oq, e);
       }
     }
     if constexpr (kPrefetch) {
@@ -733,6 +710,35 @@ __global__ __launch_bounds__(256) void conv1d_fwd_kernel(int batch, int dim, int
   store_vec<T, VEC>(y + (int64_t)b * y_bs + (int64_t)d * y_ds + t0, out);
 }
 
+// What both backward kernels share.  (The per-position dx / db / dw update is written out in each: as a shared
+// function it changes the code generated for all fifteen instances.)
+// g at one position: dy times the activation's derivative at the pre-activation
+__device__ __forceinline__ float conv1d_dact(float pre, float gj, int silu) {
+  if (silu) {
+    const float s = sigmoid_f(pre);
+    gj *= s * (1.f + pre * (1.f - s));
+  }
+  return gj;
+}
+
+// the wave's dw / db sums (xor butterfly) -> the (slice, d) row of the partials; slots >= K are never read
+template <int KM>
+__device__ __forceinline__ void conv1d_store_partials(float (&dwk)[KM], float& db, int lane, float* __restrict__ part,
+                                                      int slice, int dim, int d) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+#pragma unroll
+    for (int k = 0; k < KM; ++k) dwk[k] += __shfl_xor(dwk[k], o);
+    db += __shfl_xor(db, o);
+  }
+  if (lane == 0) {
+    float* pr = part + ((int64_t)slice * dim + d) * (kMaxK + 1);
+#pragma unroll
+    for (int k = 0; k < KM; ++k) pr[k] = dwk[k];
+    pr[kMaxK] = db;
+  }
+}
+
 // Backward.  One wave per (channel d, slice of the channel's batch x chunk
 // items): per item it recomputes the pre-activation over t0 .. t0+VEC+K-2,
 // forms g = dy * act'(pre), writes dx for its VEC positions and accumulates
@@ -795,11 +801,7 @@ __global__ __launch_bounds__(256) void conv1d_bwd_kernel(int batch, int dim, int
 #pragma unroll
       for (int k = 0; k < KM; ++k)
         if (k < K) pre = fmaf(wk[k], win[NP * VEC + j - (K - 1) + k], pre);
-      float gj = gy[j];                               // zero beyond L (loaded as 0)
-      if (silu) {
-        const float s = sigmoid_f(pre);
-        gj *= s * (1.f + pre * (1.f - s));
-      }
+      const float gj = conv1d_dact(pre, gy[j], silu);   // gy: zero beyond L (loaded as 0)
       g[j] = (t0 + j < L) ? gj : 0.f;
     }
     float out[VEC];
@@ -817,18 +819,7 @@ __global__ __launch_bounds__(256) void conv1d_bwd_kernel(int batch, int dim, int
     }
     store_vec<T, VEC>(dxr + t0, out);
   }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-#pragma unroll
-    for (int k = 0; k < KM; ++k) dwk[k] += __shfl_xor(dwk[k], o);
-    db += __shfl_xor(db, o);
-  }
-  if (lane == 0) {
-    float* pr = part + ((int64_t)slice * dim + d) * (kMaxK + 1);
-#pragma unroll
-    for (int k = 0; k < KM; ++k) pr[k] = dwk[k];   // slots >= K are never read
-    pr[kMaxK] = db;
-  }
+  conv1d_store_partials<KM>(dwk, db, lane, part, slice, dim, d);
 }
 
 // Backward for vector rows and Mamba's K = 4 (K - 1 <= VEC): lane l takes item base + l, so lane
@@ -877,11 +868,7 @@ __global__ __launch_bounds__(256) void conv1d_bwd_halo_kernel(int batch, int dim
       float pre = bv;
 #pragma unroll
       for (int k = 0; k < K; ++k) pre = fmaf(wk[k], win[VEC + j - (K - 1) + k], pre);
-      float gj = gy[j];
-      if (silu) {
-        const float s = sigmoid_f(pre);
-        gj *= s * (1.f + pre * (1.f - s));
-      }
+      const float gj = conv1d_dact(pre, gy[j], silu);
       g[j] = live ? gj : 0.f;
     }
 #pragma unroll
@@ -904,18 +891,7 @@ __global__ __launch_bounds__(256) void conv1d_bwd_halo_kernel(int batch, int dim
       store_vec<T, VEC>(dx + (int64_t)b * dx_bs + (int64_t)d * dx_ds + t0, out);
     }
   }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) dwk[k] += __shfl_xor(dwk[k], o);
-    db += __shfl_xor(db, o);
-  }
-  if (lane == 0) {
-    float* pr = part + ((int64_t)slice * dim + d) * (kMaxK + 1);
-#pragma unroll
-    for (int k = 0; k < K; ++k) pr[k] = dwk[k];
-    pr[kMaxK] = db;
-  }
+  conv1d_store_partials<K>(dwk, db, lane, part, slice, dim, d);
 }
 
 // dw[d, k] = sum_s part[s, d, k]; dbias[d] = sum_s part[s, d, kMaxK]   (fixed order)
@@ -978,12 +954,11 @@ __global__ __launch_bounds__(256) void gelu_bwd_colsum_kernel(int rows, int cols
                                                               const T* __restrict__ ga, int64_t ldga, T* __restrict__ gh,
                                                               int64_t ldgh, float* __restrict__ part) {
   constexpr int V = ElemTraits<T>::kVec;
-  __shared__ float red[3][64 * V];
   const int lane = threadIdx.x & 63, rl = threadIdx.x >> 6;
   const int cv = blockIdx.x * 64 + lane;
   const bool ok = cv < cols / V;
-  const int per = (rows + gridDim.y - 1) / gridDim.y;
-  const int r0 = blockIdx.y * per, r1 = min(rows, r0 + per);
+  int r0, r1;
+  ops::slice_range(rows, r0, r1);
   float acc[V];
 #pragma unroll
   for (int e = 0; e < V; ++e) acc[e] = 0.f;
@@ -1009,16 +984,11 @@ __global__ __launch_bounds__(256) void gelu_bwd_colsum_kernel(int rows, int cols
       for (int e = 0; e < V; ++e) acc[e] += elem_f<T>(oq, e) + (two ? elem_f<T>(oq2, e) : 0.f);
     }
   }
-  if (rl > 0) {
-#pragma unroll
-    for (int e = 0; e < V; ++e) red[rl - 1][lane * V + e] = acc[e];
-  }
-  __syncthreads();
+  __shared__ float red[3][64 * V];
+  ops::fold_stage<V>(red, acc, lane);
   if (rl == 0 && ok) {
 #pragma unroll
-    for (int e = 0; e < V; ++e)
-      part[(int64_t)blockIdx.y * cols + cv * V + e] = ((acc[e] + red[0][lane * V + e]) + red[1][lane * V + e]) +
-                                                      red[2][lane * V + e];
+    for (int e = 0; e < V; ++e) part[(int64_t)blockIdx.y * cols + cv * V + e] = ops::fold_sum<V>(red, acc[e], lane, e);
   }
 }
 
@@ -1033,7 +1003,6 @@ template <typename T>
 __global__ __launch_bounds__(256) void qkv_pack_colsum_kernel(int batch, int seq, int heads, int hd, const QkvSrc src,
                                                               T* __restrict__ out, int64_t ldo, float* __restrict__ part) {
   constexpr int V = ElemTraits<T>::kVec;
-  __shared__ float red[3][64 * V];
   const int lane = threadIdx.x & 63, rl = threadIdx.x >> 6;
   const int cols = 3 * heads * hd;
   const int cv = blockIdx.x * 64 + lane;
@@ -1047,9 +1016,8 @@ __global__ __launch_bounds__(256) void qkv_pack_colsum_kernel(int batch, int seq
   const int64_t sn = s3 == 0 ? src.sn[0] : (s3 == 1 ? src.sn[1] : src.sn[2]);
   const int64_t sh = s3 == 0 ? src.sh[0] : (s3 == 1 ? src.sh[1] : src.sh[2]);
   base += (int64_t)hh * sh + dv * V;
-  const int rows = batch * seq;
-  const int per = (rows + gridDim.y - 1) / gridDim.y;
-  const int r0 = blockIdx.y * per, r1 = min(rows, r0 + per);
+  int r0, r1;
+  ops::slice_range(batch * seq, r0, r1);
   float acc[V];
 #pragma unroll
   for (int e = 0; e < V; ++e) acc[e] = 0.f;
@@ -1062,16 +1030,11 @@ __global__ __launch_bounds__(256) void qkv_pack_colsum_kernel(int batch, int seq
       for (int e = 0; e < V; ++e) acc[e] += elem_f<T>(q, e);
     }
   }
-  if (rl > 0) {
-#pragma unroll
-    for (int e = 0; e < V; ++e) red[rl - 1][lane * V + e] = acc[e];
-  }
-  __syncthreads();
+  __shared__ float red[3][64 * V];
+  ops::fold_stage<V>(red, acc, lane);
   if (rl == 0 && ok && part) {
 #pragma unroll
-    for (int e = 0; e < V; ++e)
-      part[(int64_t)blockIdx.y * cols + cv * V + e] = ((acc[e] + red[0][lane * V + e]) + red[1][lane * V + e]) +
-                                                      red[2][lane * V + e];
+    for (int e = 0; e < V; ++e) part[(int64_t)blockIdx.y * cols + cv * V + e] = ops::fold_sum<V>(red, acc[e], lane, e);
   }
 }
 
@@ -1110,12 +1073,11 @@ __global__ __launch_bounds__(256) void colsum_slices_kernel(const float* __restr
 template <typename T, int V>
 __global__ __launch_bounds__(256) void colsum_rows_kernel(int rows, int cols, const T* __restrict__ x, int64_t ld,
                                                           float* __restrict__ part) {
-  __shared__ float red[3][64 * V];
   const int lane = threadIdx.x & 63, rl = threadIdx.x >> 6;
   const int cv = blockIdx.x * 64 + lane;
   const bool ok = cv * V < cols;
-  const int per = (rows + gridDim.y - 1) / gridDim.y;
-  const int r0 = blockIdx.y * per, r1 = min(rows, r0 + per);
+  int r0, r1;
+  ops::slice_range(rows, r0, r1);
   float acc[V];
 #pragma unroll
   for (int e = 0; e < V; ++e) acc[e] = 0.f;
@@ -1132,16 +1094,11 @@ __global__ __launch_bounds__(256) void colsum_rows_kernel(int rows, int cols, co
       for (int r = r0 + rl; r < r1; r += 4) acc[0] += to_f(x[(int64_t)r * ld + cv]);
     }
   }
-  if (rl > 0) {
-#pragma unroll
-    for (int e = 0; e < V; ++e) red[rl - 1][lane * V + e] = acc[e];
-  }
-  __syncthreads();
+  __shared__ float red[3][64 * V];
+  ops::fold_stage<V>(red, acc, lane);
   if (rl == 0 && ok) {
 #pragma unroll
-    for (int e = 0; e < V; ++e)
-      part[(int64_t)blockIdx.y * cols + cv * V + e] = ((acc[e] + red[0][lane * V + e]) + red[1][lane * V + e]) +
-                                                      red[2][lane * V + e];
+    for (int e = 0; e < V; ++e) part[(int64_t)blockIdx.y * cols + cv * V + e] = ops::fold_sum<V>(red, acc[e], lane, e);
   }
 }
 
@@ -1201,6 +1158,13 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(int rows, int cols, con
 using namespace mc;
 using namespace mc::ops;
 
+// a runtime flag as the compile-time constant `name`
+#define MC_DISPATCH_BOOL(flag, name, ...)                 \
+  do {                                                    \
+    if (flag) { constexpr bool name = true; __VA_ARGS__; } \
+    else { constexpr bool name = false; __VA_ARGS__; }     \
+  } while (0)
+
 #define MC_DISPATCH_T(dtype, ...)                                   \
   do {                                                              \
     if ((dtype) == MC_DTYPE_F32) { using T = float; __VA_ARGS__; }  \
@@ -1208,12 +1172,20 @@ using namespace mc::ops;
     else { using T = f16_t; __VA_ARGS__; }                          \
   } while (0)
 
+// The entry checks every norm shares: the dtype, then V = elements per 16-B vector and cols a whole number of
+// vectors that one wave holds in registers (rows: 0 where the entry point counts no rows).
+static int norm_check(const char* who, int dtype, int rows, int cols, int* V) {
+  MC_CHECK(dtype >= MC_DTYPE_F32 && dtype <= MC_DTYPE_F16, MC_ERR_DTYPE, "%s: bad dtype", who);
+  *V = dtype == MC_DTYPE_F32 ? 4 : 8;
+  MC_CHECK(rows >= 0 && cols > 0 && cols % *V == 0 && cols / *V <= 64 * kMaxVec, MC_ERR_SHAPE,
+           "%s: cols=%d must be a multiple of %d and <= %d", who, cols, *V, 64 * kMaxVec * *V);
+  return MC_OK;
+}
+
 extern "C" int mc_add_rmsnorm_fwd(int32_t rows, int32_t cols, int32_t dtype, const void* x, const float* res_in,
                                   const float* w, float eps, void* y, float* res_out, float* rstd, void* stream) {
-  MC_CHECK(dtype >= MC_DTYPE_F32 && dtype <= MC_DTYPE_F16, MC_ERR_DTYPE, "mc_add_rmsnorm_fwd: bad dtype");
-  const int V = dtype == MC_DTYPE_F32 ? 4 : 8;
-  MC_CHECK(rows >= 0 && cols > 0 && cols % V == 0 && cols / V <= 64 * kMaxVec, MC_ERR_SHAPE,
-           "mc_add_rmsnorm_fwd: cols=%d must be a multiple of %d and <= %d", cols, V, 64 * kMaxVec * V);
+  int V;
+  MC_TRY(norm_check("mc_add_rmsnorm_fwd", dtype, rows, cols, &V));
   if (rows == 0) return MC_OK;
   MC_CHECK(x && w && y && rstd && aligned16(x) && aligned16(y), MC_ERR_INVALID,
            "mc_add_rmsnorm_fwd: x, w, y, rstd required (x, y 16-B aligned)");
@@ -1231,10 +1203,8 @@ extern "C" size_t mc_add_rmsnorm_bwd_workspace_bytes(int32_t rows, int32_t cols)
 extern "C" int mc_add_rmsnorm_bwd(int32_t rows, int32_t cols, int32_t dtype, const void* dy, const float* dres,
                                   const float* h, const float* w, const float* rstd, void* dx, float* dres_in,
                                   float* dw, void* workspace, size_t workspace_bytes, void* stream) {
-  MC_CHECK(dtype >= MC_DTYPE_F32 && dtype <= MC_DTYPE_F16, MC_ERR_DTYPE, "mc_add_rmsnorm_bwd: bad dtype");
-  const int V = dtype == MC_DTYPE_F32 ? 4 : 8;
-  MC_CHECK(rows >= 0 && cols > 0 && cols % V == 0 && cols / V <= 64 * kMaxVec, MC_ERR_SHAPE,
-           "mc_add_rmsnorm_bwd: bad cols=%d", cols);
+  int V;
+  MC_TRY(norm_check("mc_add_rmsnorm_bwd", dtype, rows, cols, &V));
   MC_CHECK(dy && h && w && rstd && dw, MC_ERR_INVALID, "mc_add_rmsnorm_bwd: dy, h, w, rstd, dw required");
   MC_CHECK(workspace && workspace_bytes >= mc_add_rmsnorm_bwd_workspace_bytes(rows, cols), MC_ERR_WORKSPACE,
            "mc_add_rmsnorm_bwd: workspace too small");
@@ -1250,10 +1220,8 @@ extern "C" int mc_last_token_rmsnorm_fwd(int32_t batch, int32_t ntok, int32_t Lp
                                          const int64_t* tokens, int64_t pad_id, const void* x, const float* res_in,
                                          const float* w, float eps, void* y, float* h_out, float* rstd, int32_t* pos,
                                          void* stream) {
-  MC_CHECK(dtype >= MC_DTYPE_F32 && dtype <= MC_DTYPE_F16, MC_ERR_DTYPE, "mc_last_token_rmsnorm_fwd: bad dtype");
-  const int V = dtype == MC_DTYPE_F32 ? 4 : 8;
-  MC_CHECK(cols > 0 && cols % V == 0 && cols / V <= 64 * kMaxVec, MC_ERR_SHAPE,
-           "mc_last_token_rmsnorm_fwd: cols=%d must be a multiple of %d and <= %d", cols, V, 64 * kMaxVec * V);
+  int V;
+  MC_TRY(norm_check("mc_last_token_rmsnorm_fwd", dtype, 0, cols, &V));
   MC_CHECK(batch >= 0 && ntok >= 1 && Lp >= ntok, MC_ERR_SHAPE,
            "mc_last_token_rmsnorm_fwd: batch=%d, T=%d, Lp=%d: need batch >= 0 and 1 <= T <= Lp", batch, ntok, Lp);
   if (batch == 0) return MC_OK;
@@ -1270,10 +1238,8 @@ extern "C" int mc_last_token_rmsnorm_fwd(int32_t batch, int32_t ntok, int32_t Lp
 extern "C" int mc_last_token_rmsnorm_bwd(int32_t batch, int32_t Lp, int32_t cols, int32_t dtype, const void* dy,
                                          const float* h, const float* w, const float* rstd, const int32_t* pos,
                                          void* dx, float* dres_in, float* dw, void* stream) {
-  MC_CHECK(dtype >= MC_DTYPE_F32 && dtype <= MC_DTYPE_F16, MC_ERR_DTYPE, "mc_last_token_rmsnorm_bwd: bad dtype");
-  const int V = dtype == MC_DTYPE_F32 ? 4 : 8;
-  MC_CHECK(cols > 0 && cols % V == 0 && cols / V <= 64 * kMaxVec, MC_ERR_SHAPE,
-           "mc_last_token_rmsnorm_bwd: bad cols=%d", cols);
+  int V;
+  MC_TRY(norm_check("mc_last_token_rmsnorm_bwd", dtype, 0, cols, &V));
   MC_CHECK(batch >= 0 && Lp >= 1 && (int64_t)batch * Lp <= INT32_MAX, MC_ERR_SHAPE,
            "mc_last_token_rmsnorm_bwd: batch=%d, Lp=%d: need batch >= 0, Lp >= 1 and batch * Lp < 2^31", batch, Lp);
   MC_CHECK(dw && aligned16(dw), MC_ERR_INVALID, "mc_last_token_rmsnorm_bwd: dw required (16-B aligned)");
@@ -1293,10 +1259,8 @@ extern "C" int mc_last_token_rmsnorm_bwd(int32_t batch, int32_t Lp, int32_t cols
 extern "C" int mc_add_layernorm_fwd(int32_t rows, int32_t cols, int32_t dtype, const void* x, const void* res,
                                     const float* w, const float* bias, float eps, void* y, void* h_out, float* mean,
                                     float* rstd, void* stream) {
-  MC_CHECK(dtype >= MC_DTYPE_F32 && dtype <= MC_DTYPE_F16, MC_ERR_DTYPE, "mc_add_layernorm_fwd: bad dtype");
-  const int V = dtype == MC_DTYPE_F32 ? 4 : 8;
-  MC_CHECK(rows >= 0 && cols > 0 && cols % V == 0 && cols / V <= 64 * kMaxVec, MC_ERR_SHAPE,
-           "mc_add_layernorm_fwd: cols=%d must be a multiple of %d and <= %d", cols, V, 64 * kMaxVec * V);
+  int V;
+  MC_TRY(norm_check("mc_add_layernorm_fwd", dtype, rows, cols, &V));
   if (rows == 0) return MC_OK;
   MC_CHECK(x && w && y && mean && rstd && aligned16(x) && aligned16(y) && (!res || aligned16(res)) &&
                (!h_out || aligned16(h_out)),
@@ -1317,10 +1281,8 @@ extern "C" int mc_add_layernorm_bwd(int32_t rows, int32_t cols, int32_t dtype, c
                                     const void* h, const float* w, const float* mean, const float* rstd, void* dx,
                                     float* dw, float* dbias, float* dx_colsum, void* workspace,
                                     size_t workspace_bytes, void* stream) {
-  MC_CHECK(dtype >= MC_DTYPE_F32 && dtype <= MC_DTYPE_F16, MC_ERR_DTYPE, "mc_add_layernorm_bwd: bad dtype");
-  const int V = dtype == MC_DTYPE_F32 ? 4 : 8;
-  MC_CHECK(rows >= 0 && cols > 0 && cols % V == 0 && cols / V <= 64 * kMaxVec, MC_ERR_SHAPE,
-           "mc_add_layernorm_bwd: bad cols=%d", cols);
+  int V;
+  MC_TRY(norm_check("mc_add_layernorm_bwd", dtype, rows, cols, &V));
   MC_CHECK(dy && h && w && mean && rstd && dx && dw, MC_ERR_INVALID,
            "mc_add_layernorm_bwd: dy, h, w, mean, rstd, dx, dw required");
   MC_CHECK(workspace && workspace_bytes >= mc_add_layernorm_bwd_workspace_bytes(rows, cols), MC_ERR_WORKSPACE,
@@ -1328,14 +1290,9 @@ extern "C" int mc_add_layernorm_bwd(int32_t rows, int32_t cols, int32_t dtype, c
   hipStream_t s = (hipStream_t)stream;
   float* part = reinterpret_cast<float*>(workspace);
   const int kw = dx_colsum ? 3 : 2;
-  if (dx_colsum)
-    MC_DISPATCH_T(dtype, MC_DISPATCH_NV(norm_nv(cols, V), hipLaunchKernelGGL((add_layernorm_bwd_kernel<T, NV, true>),
-        dim3(kNormGrid), dim3(256), 0, s, rows, cols, (const T*)dy, (const T*)dh, (const T*)h, w, mean, rstd, (T*)dx,
-        part)));
-  else
-    MC_DISPATCH_T(dtype, MC_DISPATCH_NV(norm_nv(cols, V), hipLaunchKernelGGL((add_layernorm_bwd_kernel<T, NV, false>),
-        dim3(kNormGrid), dim3(256), 0, s, rows, cols, (const T*)dy, (const T*)dh, (const T*)h, w, mean, rstd, (T*)dx,
-        part)));
+  MC_DISPATCH_T(dtype, MC_DISPATCH_NV(norm_nv(cols, V), MC_DISPATCH_BOOL(dx_colsum != nullptr, kDxSum,
+      hipLaunchKernelGGL((add_layernorm_bwd_kernel<T, NV, kDxSum>), dim3(kNormGrid), dim3(256), 0, s, rows, cols,
+                         (const T*)dy, (const T*)dh, (const T*)h, w, mean, rstd, (T*)dx, part))));
   // part is [block][kw * cols]: dw in columns [0, cols), dbias in [cols, 2 cols), dx sums in [2 cols, 3 cols)
   colsum_two_pass(part, kNormGrid, kw * cols, cols, dw, dbias, part + (size_t)kNormGrid * 4 * kw * cols, s,
                   dx_colsum);
@@ -1346,6 +1303,13 @@ extern "C" int mc_add_layernorm_bwd(int32_t rows, int32_t cols, int32_t dtype, c
 static bool conv1d_vec_ok(const void* p, int64_t bs, int64_t ds, int V) {
   return aligned16(p) && bs % V == 0 && ds % V == 0;
 }
+
+// the tap count as a compile-time constant: 4 (Mamba's d_conv, taps unrolled) or 0 = runtime K
+#define MC_DISPATCH_KC(K, ...)                      \
+  do {                                              \
+    if ((K) == 4) { constexpr int KC = 4; __VA_ARGS__; } \
+    else { constexpr int KC = 0; __VA_ARGS__; }          \
+  } while (0)
 
 #define MC_DISPATCH_VEC(vec, ...)                                      \
   do {                                                                 \
@@ -1370,12 +1334,9 @@ extern "C" int mc_causal_conv1d_fwd(int32_t batch, int32_t dim, int32_t seqlen, 
   const dim3 grid((unsigned)((items + 255) / 256));
   const int bfast = x_bs < x_ds;   // rows adjacent in memory along the batch (channel-major views)
   MC_DISPATCH_T(dtype, MC_DISPATCH_VEC(vec, if constexpr (VEC == 1 || VEC == ElemTraits<T>::kVec) {
-    if (K == 4)
-      hipLaunchKernelGGL((conv1d_fwd_kernel<T, VEC, 4>), grid, dim3(256), 0, (hipStream_t)stream, batch, dim, seqlen,
-                         K, (const T*)x, x_bs, x_ds, w, bias, silu, (T*)y, y_bs, y_ds, bfast);
-    else
-      hipLaunchKernelGGL((conv1d_fwd_kernel<T, VEC, 0>), grid, dim3(256), 0, (hipStream_t)stream, batch, dim, seqlen,
-                         K, (const T*)x, x_bs, x_ds, w, bias, silu, (T*)y, y_bs, y_ds, bfast);
+    MC_DISPATCH_KC(K, hipLaunchKernelGGL((conv1d_fwd_kernel<T, VEC, KC>), grid, dim3(256), 0, (hipStream_t)stream, batch,
+                                         dim, seqlen, K, (const T*)x, x_bs, x_ds, w, bias, silu, (T*)y, y_bs, y_ds,
+                                         bfast));
   }));
   return check_launch("mc_causal_conv1d_fwd");
 }
@@ -1413,21 +1374,16 @@ extern "C" int mc_causal_conv1d_bwd(int32_t batch, int32_t dim, int32_t seqlen, 
   const int nslice = (total + per - 1) / per;
   const dim3 grid((unsigned)((dim + 3) / 4), (unsigned)nslice);
   MC_DISPATCH_T(dtype, MC_DISPATCH_VEC(vec, if constexpr (VEC == 1 || VEC == ElemTraits<T>::kVec) {
-    bool done = false;
+    const bool halo = VEC > 1 && K == 4;   // Mamba's d_conv on vector rows: halo g from the neighbouring lane
     if constexpr (VEC > 1) {
-      if (K == 4) {   // Mamba's d_conv on vector rows: halo g from the neighbouring lane
+      if (halo)
         hipLaunchKernelGGL((conv1d_bwd_halo_kernel<T, VEC>), grid, dim3(256), 0, s, batch, dim, seqlen, (const T*)x,
                            x_bs, x_ds, w, bias, silu, (const T*)dy, dy_bs, dy_ds, (T*)dx, dx_bs, dx_ds, per, part);
-        done = true;
-      }
     }
-    if (done) {
-    } else if (K == 4)   // taps unrolled at compile time
-      hipLaunchKernelGGL((conv1d_bwd_kernel<T, VEC, 4>), grid, dim3(256), 0, s, batch, dim, seqlen, K, (const T*)x,
-                         x_bs, x_ds, w, bias, silu, (const T*)dy, dy_bs, dy_ds, (T*)dx, dx_bs, dx_ds, per, part);
-    else
-      hipLaunchKernelGGL((conv1d_bwd_kernel<T, VEC, 0>), grid, dim3(256), 0, s, batch, dim, seqlen, K, (const T*)x,
-                         x_bs, x_ds, w, bias, silu, (const T*)dy, dy_bs, dy_ds, (T*)dx, dx_bs, dx_ds, per, part);
+    if (!halo)
+      MC_DISPATCH_KC(K, hipLaunchKernelGGL((conv1d_bwd_kernel<T, VEC, KC>), grid, dim3(256), 0, s, batch, dim, seqlen,
+                                           K, (const T*)x, x_bs, x_ds, w, bias, silu, (const T*)dy, dy_bs, dy_ds,
+                                           (T*)dx, dx_bs, dx_ds, per, part));
   }));
   const int n = dim * (K + 1);
   hipLaunchKernelGGL(conv1d_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, s, part, nslice, dim, K, dw, dbias);
@@ -1439,7 +1395,13 @@ extern "C" size_t mc_grad_colsum_workspace_bytes(int32_t rows, int32_t cols) {
   return (size_t)kGradSlices * (size_t)std::max(cols, 0) * sizeof(float);
 }
 
-static int grad_slices(int rows) { return std::max(1, std::min(kGradSlices, (rows + 31) / 32)); }
+// row slices of the fused column-sum passes: 32 rows each, at most kGradSlices
+static int slices_for(int rows) { return std::max(1, std::min(kGradSlices, (rows + 31) / 32)); }
+
+// out[c] = sum over the ns slices of part[k][c], in order
+static void launch_colsum_fold(const float* part, int ns, int cols, float* out, hipStream_t s) {
+  hipLaunchKernelGGL(colsum_slices_kernel, dim3((cols + 31) / 32), dim3(256), 0, s, part, ns, cols, out);
+}
 
 extern "C" int mc_gelu_bwd(int32_t rows, int32_t cols, int32_t dtype, const void* h, int64_t ldh, const void* ga,
                            int64_t ldga, void* gh, int64_t ldgh, float* dbias, void* workspace,
@@ -1458,11 +1420,11 @@ extern "C" int mc_gelu_bwd(int32_t rows, int32_t cols, int32_t dtype, const void
            "mc_gelu_bwd: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   float* part = reinterpret_cast<float*>(workspace);
-  const int ns = grad_slices(rows);
+  const int ns = slices_for(rows);
   const dim3 grid((unsigned)((cols / V + 63) / 64), (unsigned)ns);
   MC_DISPATCH_T(dtype, hipLaunchKernelGGL((gelu_bwd_colsum_kernel<T>), grid, dim3(256), 0, s, rows, cols,
                                           (const T*)h, ldh, (const T*)ga, ldga, (T*)gh, ldgh, part));
-  hipLaunchKernelGGL(colsum_slices_kernel, dim3((cols + 31) / 32), dim3(256), 0, s, part, ns, cols, dbias);
+  launch_colsum_fold(part, ns, cols, dbias, s);
   return check_launch("mc_gelu_bwd");
 }
 
@@ -1489,12 +1451,11 @@ extern "C" int mc_qkv_grad_pack(const mc_qkv_pack_params* p, void* stream) {
            MC_ERR_WORKSPACE, "mc_qkv_grad_pack: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   float* part = p->dbias ? reinterpret_cast<float*>(p->workspace) : nullptr;
-  const int ns = grad_slices(rows);
+  const int ns = slices_for(rows);
   const dim3 grid((unsigned)((cols / V + 63) / 64), (unsigned)ns);
   MC_DISPATCH_T(p->dtype, hipLaunchKernelGGL((qkv_pack_colsum_kernel<T>), grid, dim3(256), 0, s, p->batch, p->seq,
                                              p->heads, p->head_dim, src, (T*)p->out, p->ld_out, part));
-  if (p->dbias)
-    hipLaunchKernelGGL(colsum_slices_kernel, dim3((cols + 31) / 32), dim3(256), 0, s, part, ns, cols, p->dbias);
+  if (p->dbias) launch_colsum_fold(part, ns, cols, p->dbias, s);
   return check_launch("mc_qkv_grad_pack");
 }
 
@@ -1741,10 +1702,8 @@ extern "C" int mc_sum_slabs(int32_t s, int64_t n, const float* src, int64_t slab
 }
 
 // ------------------------------------------------------------------ column sums, row L2-normalize (C-ABI)
-static int colsum_slices(int rows) { return std::max(1, std::min(kGradSlices, (rows + 31) / 32)); }
-
 extern "C" size_t mc_colsum_workspace_bytes(int32_t rows, int32_t cols) {
-  return (size_t)colsum_slices(std::max(rows, 0)) * (size_t)std::max(cols, 0) * sizeof(float);
+  return (size_t)slices_for(std::max(rows, 0)) * (size_t)std::max(cols, 0) * sizeof(float);
 }
 
 extern "C" int mc_colsum(int32_t rows, int32_t cols, int32_t dtype, const void* x, int64_t ld, float* out,
@@ -1762,7 +1721,7 @@ extern "C" int mc_colsum(int32_t rows, int32_t cols, int32_t dtype, const void* 
   MC_CHECK(x && workspace && workspace_bytes >= mc_colsum_workspace_bytes(rows, cols), MC_ERR_WORKSPACE,
            "mc_colsum: x and a workspace of mc_colsum_workspace_bytes required");
   float* part = reinterpret_cast<float*>(workspace);
-  const int ns = colsum_slices(rows);
+  const int ns = slices_for(rows);
   const int V = dtype == MC_DTYPE_F32 ? 4 : 8;
   const bool vec = cols % V == 0 && ld % V == 0 && aligned16(x);
   MC_DISPATCH_T(dtype, {
@@ -1773,7 +1732,7 @@ extern "C" int mc_colsum(int32_t rows, int32_t cols, int32_t dtype, const void* 
       hipLaunchKernelGGL((colsum_rows_kernel<T, 1>), dim3((unsigned)((cols + 63) / 64), ns), dim3(256), 0, s, rows,
                          cols, (const T*)x, ld, part);
   });
-  hipLaunchKernelGGL(colsum_slices_kernel, dim3((cols + 31) / 32), dim3(256), 0, s, part, ns, cols, out);
+  launch_colsum_fold(part, ns, cols, out, s);
   return check_launch("mc_colsum");
 }
 
@@ -1807,7 +1766,6 @@ extern "C" int mc_colsum_fold(int32_t nslices, int32_t cols, const float* part, 
   MC_CHECK(nslices >= 1 && cols >= 0, MC_ERR_SHAPE, "mc_colsum_fold: bad shape (nslices %d, cols %d)", nslices, cols);
   if (cols == 0) return MC_OK;
   MC_CHECK(part && out, MC_ERR_INVALID, "mc_colsum_fold: null pointer");
-  hipLaunchKernelGGL(colsum_slices_kernel, dim3((cols + 31) / 32), dim3(256), 0, (hipStream_t)stream, part, nslices, cols,
-                     out);
+  launch_colsum_fold(part, nslices, cols, out, (hipStream_t)stream);
   return check_launch("mc_colsum_fold");
 }
