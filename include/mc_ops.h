@@ -16,6 +16,9 @@
  *                           SS2D's depthwise conv, model.py:331-339)
  *   mc_patch_embed_input     the image input path: float NCHW or raw uint8 NHWC images ->
  *                           normalised patch rows for the patch-embed GEMM in one pass
+ *   mc_patch_embed_input_gather, mc_token_embed_gather_fwd/bwd  patch dropout: the same rows for a
+ *                           kept subset of each image's patches, and the token embedding (class token +
+ *                           each kept patch's own position row) with its deterministic table gradient
  *   mc_patch_im2col          ViT / VSSM patch-embed input reshuffle: stride ==
  *                           kernel conv as a GEMM (model.py:189-191 PatchEmbed2D)
  * Same conventions as mc_scan.h: device pointers, caller-owned buffers,
@@ -122,6 +125,47 @@ typedef struct mc_patch_input_params {
   void* out;
 } mc_patch_input_params;
 int mc_patch_embed_input(const mc_patch_input_params* p, void* stream);
+
+/* Patch dropout (FLIP; open_clip PatchDropout with exclude_first_token): in training each image keeps
+ * n_keep of its n = ph*pw patches plus the class token, so everything behind the patch embedding runs
+ * on batch * (n_keep + 1) token rows.  The reference declares --force-patch-dropout (cli/main.py:73,
+ * 355-356) and never builds it.
+ *
+ * mc_patch_embed_input_gather: mc_patch_embed_input for the kept patches only,
+ *   out[b*n_keep + s, :] = the row mc_patch_embed_input writes for patch keep[b, s] of image b
+ * (same column order, casts and scale / shift rule); out is (batch*n_keep, C*P*P).  keep: (batch, n_keep)
+ * int32, 1 <= n_keep <= ph*pw, any order, duplicates allowed.  The kernel clamps every index into
+ * [0, ph*pw) before use, so no index value can address outside its image. */
+int mc_patch_embed_input_gather(const mc_patch_input_params* p, const int32_t* keep, int32_t n_keep, void* stream);
+
+/* The ViT token embedding over the kept patches and its position-table gradient (rnd = round to dtype,
+ * adds in fp32):
+ *   fwd: out[b, 0]     = rnd(rnd(cls) + rnd(pos[0]))
+ *        out[b, 1 + s] = rnd(x[b, s] + rnd(pos[1 + keep[b, s]]))       -- each patch's own position row;
+ *        the bits of cat([cls.to(dtype), x], 1) + pos.to(dtype) on those rows.  keep is clamped into [0, n).
+ *   bwd: dpos[0]     = sum_b dm[b, 0]
+ *        dpos[1 + j] = sum over {b : 0 <= slot[b, j] < n_keep} of dm[b, 1 + slot[b, j]]
+ *        in fp32, the samples added in the order b = 0, 1, ... by the one thread that owns the element (no
+ *        atomics, no workspace): deterministic.  Every row of dpos is written; a position no sample kept
+ *        becomes exact zeros (no memset by the caller).  d cls = dpos[0]; d x = dm[:, 1:].
+ * cls (cols,), pos (n + 1, cols), dpos (n + 1, cols): fp32.  x (batch, n_keep, cols), out and dm
+ * (batch, n_keep + 1, cols): contiguous in dtype (f32 / bf16 / f16).  keep (batch, n_keep) int32; slot
+ * (batch, n) int32, the inverse map: the row of patch j among sample b's kept ones, any value outside
+ * [0, n_keep) = not kept.  16-B vectors: cols % 8 == 0 (16-bit) / % 4 == 0 (f32), else MC_ERR_SHAPE;
+ * 16-B aligned buffers.  fwd reads cls, pos, x, keep and writes out; bwd reads dm, slot and writes dpos. */
+typedef struct mc_token_embed_gather_params {
+  int32_t batch, n, n_keep, cols, dtype, reserved;
+  const float* cls;
+  const float* pos;
+  const void* x;
+  const int32_t* keep;
+  void* out;
+  const void* dm;
+  const int32_t* slot;
+  float* dpos;
+} mc_token_embed_gather_params;
+int mc_token_embed_gather_fwd(const mc_token_embed_gather_params* p, void* stream);
+int mc_token_embed_gather_bwd(const mc_token_embed_gather_params* p, void* stream);
 
 /* Fused gradient passes that also produce the bias gradient of the GEMM in
  * front of them, in the same single stream over the (rows x cols) gradient

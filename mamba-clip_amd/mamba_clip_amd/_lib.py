@@ -263,6 +263,15 @@ class PatchInputParams(ctypes.Structure):
     ]
 
 
+class TokenEmbedGatherParams(ctypes.Structure):
+    """Mirror of ``mc_token_embed_gather_params`` (include/mc_ops.h)."""
+    _fields_ = [
+        ("batch", c_i32), ("n", c_i32), ("n_keep", c_i32), ("cols", c_i32), ("dtype", c_i32), ("reserved", c_i32),
+        ("cls", c_fp), ("pos", c_fp), ("x", c_vp), ("keep", c_vp), ("out", c_vp),
+        ("dm", c_vp), ("slot", c_vp), ("dpos", c_fp),
+    ]
+
+
 # symbol -> (restype, argtypes); every entry point include/*.h declares
 SYMBOLS = {
     "mc_last_error": (ctypes.c_char_p, []),
@@ -336,6 +345,9 @@ SYMBOLS = {
     "mc_attn_masked_fwd": (ctypes.c_int, [ctypes.POINTER(AttnMaskedFwdParams), c_vp]),
     "mc_attn_masked_bwd": (ctypes.c_int, [ctypes.POINTER(AttnMaskedBwdParams), c_vp]),
     "mc_patch_embed_input": (ctypes.c_int, [ctypes.POINTER(PatchInputParams), c_vp]),
+    "mc_patch_embed_input_gather": (ctypes.c_int, [ctypes.POINTER(PatchInputParams), c_vp, c_i32, c_vp]),
+    "mc_token_embed_gather_fwd": (ctypes.c_int, [ctypes.POINTER(TokenEmbedGatherParams), c_vp]),
+    "mc_token_embed_gather_bwd": (ctypes.c_int, [ctypes.POINTER(TokenEmbedGatherParams), c_vp]),
     "mc_ss2d_conv_stack_fwd": (ctypes.c_int, [ctypes.POINTER(SS2DConvParams), c_vp]),
     "mc_ss2d_conv_stack_bwd": (ctypes.c_int, [ctypes.POINTER(SS2DConvBwdParams), c_vp]),
     "mc_ss2d_conv_bwd_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32, c_i32, c_i32]),

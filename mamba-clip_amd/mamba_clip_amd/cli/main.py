@@ -17,6 +17,13 @@ import time
 import torch
 
 
+def _patch_dropout_value(text):
+    v = float(text)
+    if not 0.0 <= v < 1.0:
+        raise argparse.ArgumentTypeError(f"must be in [0, 1), got {text}")
+    return v
+
+
 def build_parser():
     p = argparse.ArgumentParser("mamba-clip", description=__doc__.split("\n")[0])
     p.add_argument("--data-path", type=str, default=None, help="CSV data path (not supported: use --synthetic)")
@@ -66,6 +73,11 @@ def build_parser():
                         "logit_scale = log 10 and logit_bias = -10; --local-loss and --gather-with-grad are "
                         "ignored (each rank always scores its images against all texts, gathered with "
                         "gradients); with --stage 2 it only changes the frozen model's initialisation")
+    p.add_argument("--force-patch-dropout", type=_patch_dropout_value, default=None, metavar="FLOAT",
+                   help="stage 1: train the ViT image tower on a random subset of each image's patches, dropping "
+                        "this fraction in [0, 1) (FLIP / open_clip PatchDropout; the class token is always kept, "
+                        "evaluation sees whole images); accepted and ignored with --stage 2, whose frozen towers "
+                        "see whole images")
     p.add_argument("--accum-freq", type=int, default=1)
     p.add_argument("--dist-url", type=str, default="env://")
     p.add_argument("--dist-backend", type=str, default="nccl")
@@ -103,6 +115,8 @@ def build_model(args, device):
     model_kwargs = {}
     if getattr(args, "siglip", False):        # pipeline.py:213-216
         model_kwargs = dict(init_logit_scale=math.log(10), init_logit_bias=-10)
+    if args.stage == 1 and getattr(args, "force_patch_dropout", None) is not None:
+        model_kwargs["force_patch_dropout"] = args.force_patch_dropout
     model, _, _, _ = init_model(name, **model_kwargs)
     if args.stage == 1:
         if args.lock_image:

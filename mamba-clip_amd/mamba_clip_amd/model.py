@@ -34,9 +34,10 @@ import torch.utils.checkpoint
 
 from . import GEMM_GRIDS_DATA_PARALLEL
 from .ops import (GradHandoff, GradSlab, _compute_dtype, add_layernorm, add_pos, add_rmsnorm, attn_supported,
-                  causal_conv1d, l2_normalize, last_token_rmsnorm, linear_sk, mlp, neg_exp_many, pack_key_mask,
-                  packed_attention, patch_im2col, qkv_proj, split_rows, split_rows_n, ss2d_conv_stack,
-                  ss2d_merge_ln_gate, ss2d_proj, ss2d_proj_ok, token_embed, weight_cast_scope, wleft_mm)
+                  causal_conv1d, keep_slots, l2_normalize, last_token_rmsnorm, linear_sk, mlp, neg_exp_many,
+                  pack_key_mask, packed_attention, patch_im2col, patch_keep_indices, qkv_proj, split_rows,
+                  split_rows_n, ss2d_conv_stack, ss2d_merge_ln_gate, ss2d_proj, ss2d_proj_ok, token_embed,
+                  token_embed_gather, weight_cast_scope, wleft_mm)
 from .selective_scan_interface import (SS2D_REVERSE_GROUPS, SS2D_U_GROUPS, SelectiveScanFn, fine_state_scope,
                                        grouped_scan_fn, selective_scan_fn)
 
@@ -267,12 +268,21 @@ class PatchEmbed(nn.Module):
         self.patch, self.grid = patch, img_size // patch
         self.proj = nn.Conv2d(in_chans, dim, patch, patch, bias=bias)
 
-    def forward(self, x):  # (B, C, H, W) float, or (B, H, W, C) uint8 raw images -> (B, H/P * W/P, dim)
+    def forward(self, x, keep=None):
+        """(B, C, H, W) float, or (B, H, W, C) uint8 raw images -> (B, H/P * W/P, dim); with keep
+        ((B, n_keep) int32 patch indices, patch dropout) only those patches: (B, n_keep, dim)."""
         Bsz = x.shape[0]
         dt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else (
             torch.float32 if x.dtype == torch.uint8 else x.dtype)
         # the input cast (and for raw images ToTensor + Normalize) happens inside the patch kernel
-        cols = patch_im2col(x, self.patch, dt)
+        if keep is None:
+            cols = patch_im2col(x, self.patch, dt)
+        elif x.is_cuda:   # the gather kernel reads the kept patches only: the GEMM below shrinks with them
+            cols = patch_im2col(x, self.patch, dt, keep=keep)
+        else:             # off the GPU: every patch's row, the kept ones picked with torch
+            cols = patch_im2col(x, self.patch, dt)
+            idx = keep.long()[:, :, None].expand(-1, -1, cols.shape[1])
+            cols = cols.view(Bsz, -1, cols.shape[1]).gather(1, idx).reshape(-1, cols.shape[1])
         w = self.proj.weight.reshape(self.proj.weight.shape[0], -1)
         if cols.is_cuda:   # split-K weight gradient (ops.wgrad): 188 -> 85 us at C2
             out = linear_sk(cols, w, self.proj.bias)
@@ -361,10 +371,26 @@ class ViTBlock(nn.Module):
 
 
 class VisionTransformer(nn.Module):
-    """ViT-B/16 image tower: (B, 3, 224, 224) -> (B, output_dim)."""
+    """ViT-B/16 image tower: (B, 3, 224, 224) -> (B, output_dim).
 
-    def __init__(self, img_size=224, patch=16, width=768, layers=12, heads=12, output_dim=512):
+    patch_dropout = p (FLIP; open_clip's PatchDropout with exclude_first_token=True, the reference's
+    --force-patch-dropout): while the module is training and 0 < p < 1, every image keeps a uniformly
+    random subset of n_keep = max(1, int(n * (1 - p))) of its n patches plus the class token, each kept
+    patch with the position row of its original place, and the blocks run on n_keep + 1 tokens.  The
+    kept patches stay in ascending patch order (memory order) where open_clip leaves them in topk
+    order: behind the position add the tower is permutation-equivariant over the patch tokens and it
+    pools the class row, so the features do not depend on that order.  In eval() or with p == 0 the
+    forward runs the ops it runs without the option.  The indices come from torch's generator of the
+    input's device (ops.patch_keep_indices: torch.manual_seed governs them, no host sync);
+    `last_keep` holds those of the latest dropped forward, None after a full one."""
+
+    last_keep = None
+
+    def __init__(self, img_size=224, patch=16, width=768, layers=12, heads=12, output_dim=512, patch_dropout=0.0):
         super().__init__()
+        if not 0.0 <= patch_dropout < 1.0:
+            raise ValueError(f"VisionTransformer: patch_dropout must be in [0, 1), got {patch_dropout}")
+        self.patch_dropout = float(patch_dropout)
         self.output_dim = output_dim
         self.patch_embed = PatchEmbed(img_size, patch, 3, width)
         n = (img_size // patch) ** 2
@@ -379,10 +405,27 @@ class VisionTransformer(nn.Module):
                 if m.bias is not None:
                     nn.init.zeros_(m.bias)
 
-    def forward(self, x):
-        x = self.patch_embed(x)
-        # cat([cls, x]) + pos with a deterministic backward (ops.TokenEmbedFn)
-        m, h = token_embed(self.cls_token, x, self.pos_embed), None
+    def patch_dropout_active(self):
+        return self.training and 0.0 < self.patch_dropout < 1.0
+
+    def forward(self, x, keep=None):
+        """keep ((B, n_keep) distinct patch indices per image) replaces the random draw; it is there for
+        tests and is honoured in training mode only."""
+        if self.training and (keep is not None or self.patch_dropout_active()):
+            # the selection sits in front of the blocks: gradient checkpointing recomputes blocks only
+            n = self.pos_embed.shape[1] - 1
+            if keep is None:
+                keep, slot = patch_keep_indices(x.shape[0], n, max(1, int(n * (1.0 - self.patch_dropout))), x.device)
+            else:
+                keep = keep.to(device=x.device, dtype=torch.int32)
+                slot = keep_slots(keep, n)
+            self.last_keep = keep
+            m, h = token_embed_gather(self.cls_token, self.patch_embed(x, keep), self.pos_embed, keep, slot), None
+        else:
+            self.last_keep = None
+            x = self.patch_embed(x)
+            # cat([cls, x]) + pos with a deterministic backward (ops.TokenEmbedFn)
+            m, h = token_embed(self.cls_token, x, self.pos_embed), None
         m, h = _run_blocks(self.blocks, m, h, self.grad_checkpointing and torch.is_grad_enabled())
         # final norm on the pooled (cls) rows only: same values as norm(x)[:, 0]
         y, _ = add_layernorm(m[:, 0], h[:, 0], self.norm.weight, self.norm.bias, self.norm.eps)
@@ -1031,11 +1074,12 @@ MODEL_CONFIGS = {
 }
 
 
-def build_clip(name, **clip_kwargs):
+def build_clip(name, force_patch_dropout=None, **clip_kwargs):
     """``clip_kwargs`` (init_logit_scale, init_logit_bias) go to ClipModel: SigLIP training starts from
-    log 10 and -10 (pipeline.py:213-216)."""
+    log 10 and -10 (pipeline.py:213-216).  ``force_patch_dropout`` (None = 0) is the visual tower's
+    patch_dropout (the reference's --force-patch-dropout, cli/main.py:355-356)."""
     cfg = MODEL_CONFIGS[name]
-    visual = VisionTransformer(**cfg["vision"])
+    visual = VisionTransformer(**cfg["vision"], patch_dropout=force_patch_dropout or 0.0)
     if "hf_bert" in cfg:
         text = HFBertTextEncoder(**cfg["hf_bert"])
     else:
@@ -1045,7 +1089,8 @@ def build_clip(name, **clip_kwargs):
 
 def init_model(model, tokenizer=None, aug_cfg=None, is_clip=False, use_tokenizer=False, **model_kwargs):
     """Returns (model, preprocess_train, preprocess_val, tokenizer) like model.py:1257-1289.
-    ``model_kwargs`` (init_logit_scale, init_logit_bias) reach the ClipModel a config name builds.
+    ``model_kwargs`` (init_logit_scale, init_logit_bias, force_patch_dropout) reach build_clip for a
+    config name: the ClipModel's initial scale / bias and the visual tower's patch dropout.
 
     "medmamba" -> VSSM(depths=[2,2,8,2], dims=[64,128,256,512], num_classes=2);
     a MODEL_CONFIGS name -> a random-init ClipModel (no hub access offline);

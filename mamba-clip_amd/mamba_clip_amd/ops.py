@@ -14,8 +14,8 @@ Contrastive ops (include/mc_contrastive.h), at the head of the file:
 ``retrieval_ranks(X, Y, scale)``  evaluation: per-row / per-column counts of logits that beat or
                           tie the label's, plus LSE and loss, again without the logits in
                           memory (mc_retrieval_ranks).
-Then the encoder ops (mc_ops.h: the fused norms, causal conv1d, patch im2col, L2 normalisation, the
-per-forward weight casts), the towers' projections (mc_gemm.h: ``wgrad``, ``linear_sk``, ``wleft_mm``,
+Then the encoder ops (mc_ops.h: the fused norms, causal conv1d, patch im2col, patch dropout's gather
+forms of it and of the token embedding, L2 normalisation, the per-forward weight casts), the towers' projections (mc_gemm.h: ``wgrad``, ``linear_sk``, ``wleft_mm``,
 ``linear_hip``, ``mlp``, ``qkv_proj``), the packed short-sequence attention (mc_attn.h) and the SS2D
 cross-scan glue (mc_ss2d.h).  The selective scan has its own module (selective_scan_interface.py).
 All launches go on the current HIP stream; nothing synchronises.
@@ -841,6 +841,67 @@ def _norm_affine(device, C, mean, std):
     return _NORM_CACHE[key]
 
 
+def patch_keep_indices(batch, n, n_keep, device, generator=None):
+    """Patch dropout's selection (open_clip PatchDropout): every sample keeps a uniformly random subset of
+    n_keep distinct patches out of n, drawn from torch's generator of `device` (torch.manual_seed governs
+    it; no host sync).  Returns (keep, slot), int32: keep (batch, n_keep) the kept patch indices in
+    ascending order, slot (batch, n) the inverse map -- slot[b, keep[b, s]] = s, -1 for a dropped patch."""
+    order = torch.rand(batch, n, device=device, generator=generator).argsort(dim=1)
+    keep = order[:, :n_keep].sort(dim=1).values
+    return keep.to(torch.int32), keep_slots(keep, n)
+
+
+def keep_slots(keep, n):
+    """The inverse map of a (batch, n_keep) table of distinct patch indices: (batch, n) int32, -1 = dropped."""
+    batch, n_keep = keep.shape
+    slot = torch.full((batch, n), -1, device=keep.device, dtype=torch.int32)
+    rows = torch.arange(n_keep, device=keep.device, dtype=torch.int32).expand(batch, n_keep)
+    return slot.scatter_(1, keep.long(), rows)
+
+
+def _patch_rows(img, patch, out_dtype, mean, std, keep=None):
+    """The patch rows of PatchIm2colFn / PatchIm2colGatherFn and the backward's meta tuple."""
+    lib = _lib.load()
+    u8 = img.dtype == torch.uint8
+    img = img.contiguous()
+    if u8:
+        Bsz, H, W, C = img.shape
+    else:
+        Bsz, C, H, W = img.shape
+    out_dtype = out_dtype or (torch.float32 if u8 else img.dtype)
+    n = (H // patch) * (W // patch)
+    if keep is not None:
+        if keep.dtype != torch.int32 or keep.dim() != 2 or keep.shape[0] != Bsz or keep.device != img.device:
+            raise RuntimeError(f"patch_im2col: keep must be a (batch, n_keep) int32 tensor on the images' device "
+                               f"(got {tuple(keep.shape)} {keep.dtype} on {keep.device})")
+        if patch % 4:
+            raise RuntimeError("patch_im2col: keep needs a patch size that is a multiple of 4")
+        keep = keep.contiguous()
+    rows = n if keep is None else keep.shape[1]
+    out = torch.empty(Bsz * rows, C * patch * patch, device=img.device, dtype=out_dtype)
+    if patch % 4 == 0:
+        p = _lib.PatchInputParams()
+        p.batch, p.channels, p.height, p.width, p.patch = Bsz, C, H, W, patch
+        p.layout = _lib.MC_LAYOUT_NHWC if u8 else _lib.MC_LAYOUT_NCHW
+        p.in_dtype, p.out_dtype = _lib.dtype_code(img.dtype), _lib.dtype_code(out_dtype)
+        if u8:
+            sc, sh = _norm_affine(img.device, C, mean or IMAGE_MEAN, std or IMAGE_STD)
+            p.scale, p.shift = sc.data_ptr(), sh.data_ptr()
+        p.img, p.out = img.data_ptr(), out.data_ptr()
+        if keep is None:
+            _lib.check(lib.mc_patch_embed_input(ctypes.byref(p), _lib.stream_handle(img.device)), "mc_patch_embed_input")
+        else:
+            _lib.check(lib.mc_patch_embed_input_gather(ctypes.byref(p), keep.data_ptr(), rows,
+                                                       _lib.stream_handle(img.device)), "mc_patch_embed_input_gather")
+    else:   # VSSM's P = 4 goes here too; other P (not a multiple of 4): element-wise kernel, same dtype
+        if u8:
+            raise RuntimeError("patch_im2col: uint8 images need a patch size that is a multiple of 4")
+        src = img if img.dtype == out_dtype else img.to(out_dtype)
+        _lib.check(lib.mc_patch_im2col(Bsz, C, H, W, patch, _lib.dtype_code(out_dtype), src.data_ptr(),
+                                       out.data_ptr(), _lib.stream_handle(img.device)), "mc_patch_im2col")
+    return out, (Bsz, C, H, W, patch, img.dtype)
+
+
 class PatchIm2colFn(torch.autograd.Function):
     """Non-overlapping (k = s = P) patch rows in `out_dtype`, the input cast fused in (float NCHW), or
     the whole image input path for raw uint8 NHWC images (ToTensor + Normalize + patchify,
@@ -849,32 +910,7 @@ class PatchIm2colFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, img, patch, out_dtype, mean, std):
-        lib = _lib.load()
-        u8 = img.dtype == torch.uint8
-        img = img.contiguous()
-        if u8:
-            Bsz, H, W, C = img.shape
-        else:
-            Bsz, C, H, W = img.shape
-        out_dtype = out_dtype or (torch.float32 if u8 else img.dtype)
-        out = torch.empty(Bsz * (H // patch) * (W // patch), C * patch * patch, device=img.device, dtype=out_dtype)
-        if patch % 4 == 0:
-            p = _lib.PatchInputParams()
-            p.batch, p.channels, p.height, p.width, p.patch = Bsz, C, H, W, patch
-            p.layout = _lib.MC_LAYOUT_NHWC if u8 else _lib.MC_LAYOUT_NCHW
-            p.in_dtype, p.out_dtype = _lib.dtype_code(img.dtype), _lib.dtype_code(out_dtype)
-            if u8:
-                sc, sh = _norm_affine(img.device, C, mean or IMAGE_MEAN, std or IMAGE_STD)
-                p.scale, p.shift = sc.data_ptr(), sh.data_ptr()
-            p.img, p.out = img.data_ptr(), out.data_ptr()
-            _lib.check(lib.mc_patch_embed_input(ctypes.byref(p), _lib.stream_handle(img.device)), "mc_patch_embed_input")
-        else:   # VSSM's P = 4 goes here too; other P (not a multiple of 4): element-wise kernel, same dtype
-            if u8:
-                raise RuntimeError("patch_im2col: uint8 images need a patch size that is a multiple of 4")
-            src = img if img.dtype == out_dtype else img.to(out_dtype)
-            _lib.check(lib.mc_patch_im2col(Bsz, C, H, W, patch, _lib.dtype_code(out_dtype), src.data_ptr(),
-                                           out.data_ptr(), _lib.stream_handle(img.device)), "mc_patch_im2col")
-        ctx.meta = (Bsz, C, H, W, patch, img.dtype)
+        out, ctx.meta = _patch_rows(img, patch, out_dtype, mean, std)
         return out
 
     @staticmethod
@@ -886,11 +922,36 @@ class PatchIm2colFn(torch.autograd.Function):
         return gi.to(in_dt), None, None, None, None
 
 
-def patch_im2col(img, patch, out_dtype=None, mean=None, std=None):
+class PatchIm2colGatherFn(torch.autograd.Function):
+    """PatchIm2colFn for the patches keep[b] ((B, n_keep) int32) of each image only
+    (mc_patch_embed_input_gather: patch dropout).  The backward scatters the rows into zeros and then
+    takes PatchIm2colFn's (torch: a float image's gradient is no hot path)."""
+
+    @staticmethod
+    def forward(ctx, img, patch, out_dtype, mean, std, keep):
+        out, ctx.meta = _patch_rows(img, patch, out_dtype, mean, std, keep)
+        ctx.keep = keep
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        Bsz, C, H, W, P, in_dt = ctx.meta
+        if in_dt == torch.uint8:
+            return None, None, None, None, None, None
+        n, K = (H // P) * (W // P), g.shape[1]
+        idx = ctx.keep.long().clamp(0, n - 1)[:, :, None].expand(-1, -1, K)
+        full = torch.zeros(Bsz, n, K, device=g.device, dtype=g.dtype).scatter_add_(1, idx, g.view(Bsz, -1, K))
+        return PatchIm2colFn.backward(ctx, full.view(Bsz * n, K))[0], None, None, None, None, None
+
+
+def patch_im2col(img, patch, out_dtype=None, mean=None, std=None, keep=None):
     """(B, C, H, W) float -> (B * H/P * W/P, C * P * P) patch rows (row = (b, h/P, w/P), col = (c, ph, pw)),
     cast to out_dtype on the way; or (B, H, W, C) uint8 raw images -> the same rows normalised with
-    mean / std (default open_clip's OPENAI_DATASET_MEAN / _STD, the reference's transform)."""
-    return PatchIm2colFn.apply(img, patch, out_dtype, mean, std)
+    mean / std (default open_clip's OPENAI_DATASET_MEAN / _STD, the reference's transform).
+    keep ((B, n_keep) int32 patch indices, patch dropout): only rows (b, keep[b, s]), (B * n_keep, C * P * P)."""
+    if keep is None:
+        return PatchIm2colFn.apply(img, patch, out_dtype, mean, std)
+    return PatchIm2colGatherFn.apply(img, patch, out_dtype, mean, std, keep)
 
 
 # ---------------------------------------------------------------------------- projections with split-K weight grads
@@ -1082,6 +1143,78 @@ def token_embed(cls, x, pos):
     if x.is_cuda and cls.requires_grad and pos.requires_grad:
         return TokenEmbedFn.apply(cls, x, pos)
     return torch.cat([cls.to(x.dtype).expand(x.shape[0], -1, -1), x], dim=1) + pos.to(x.dtype)
+
+
+def _token_embed_gather_torch(cls, x, pos, keep):
+    """The kernels' math in torch index ops: the full table cast to x's dtype, each kept patch's row gathered."""
+    B, _, C = x.shape
+    pe = pos.to(x.dtype)
+    rows = pe[:, 1:].expand(B, -1, -1).gather(1, keep.long()[:, :, None].expand(-1, -1, C))
+    return torch.cat([cls.to(x.dtype).expand(B, -1, -1) + pe[:, :1], x + rows], dim=1)
+
+
+def _token_embed_vec_ok(x):
+    """The shapes the 16-B-vector kernels take (others get MC_ERR_SHAPE from the C entry points)."""
+    vec = {torch.float32: 4, torch.bfloat16: 8, torch.float16: 8}.get(x.dtype)
+    return x.is_cuda and vec is not None and x.shape[-1] % vec == 0 and x.shape[0] > 0
+
+
+def _token_embed_params(B, n, n_keep, C, dtype):
+    p = _lib.TokenEmbedGatherParams()
+    p.batch, p.n, p.n_keep, p.cols, p.dtype = B, n, n_keep, C, _lib.dtype_code(dtype)
+    return p
+
+
+class TokenEmbedGatherFn(torch.autograd.Function):
+    """TokenEmbedFn for patch dropout: m[b] = [cls + pos[0], x[b, s] + pos[1 + keep[b, s]] ...], x the
+    embeddings of the kept patches only (mc_token_embed_gather_fwd: the bits of the torch expression).
+    Backward: d pos from dm through the inverse map `slot` in one deterministic pass that writes the
+    whole table, zeros at positions nobody kept (mc_token_embed_gather_bwd); d cls = d pos[0];
+    d x = the view dm[:, 1:]."""
+
+    @staticmethod
+    def forward(ctx, cls, x, pos, keep, slot):
+        B, K, C = x.shape
+        x = x.contiguous()
+        cls32, pos32 = cls.detach().float().contiguous(), pos.detach().float().contiguous()
+        m = torch.empty(B, K + 1, C, device=x.device, dtype=x.dtype)
+        p = _token_embed_params(B, slot.shape[1], K, C, x.dtype)
+        p.cls, p.pos, p.x, p.keep, p.out = cls32.data_ptr(), pos32.data_ptr(), x.data_ptr(), keep.data_ptr(), m.data_ptr()
+        _lib.check(_lib.load().mc_token_embed_gather_fwd(ctypes.byref(p), _lib.stream_handle(x.device)),
+                   "mc_token_embed_gather_fwd")
+        ctx.save_for_backward(slot)
+        ctx.meta = (cls.dtype, pos.dtype, K)
+        return m
+
+    @staticmethod
+    def backward(ctx, dm):
+        (slot,) = ctx.saved_tensors
+        cls_dt, pos_dt, K = ctx.meta
+        B, _, C = dm.shape
+        dm = dm.contiguous()
+        n = slot.shape[1]
+        dpos = torch.empty(1, n + 1, C, device=dm.device, dtype=torch.float32)
+        p = _token_embed_params(B, n, K, C, dm.dtype)
+        p.dm, p.slot, p.dpos = dm.data_ptr(), slot.data_ptr(), dpos.data_ptr()
+        _lib.check(_lib.load().mc_token_embed_gather_bwd(ctypes.byref(p), _lib.stream_handle(dm.device)),
+                   "mc_token_embed_gather_bwd")
+        dcls = dpos[:, :1].clone()
+        return dcls.to(cls_dt), dm[:, 1:], dpos.to(pos_dt), None, None
+
+
+def token_embed_gather(cls, x, pos, keep, slot):
+    """The ViT token embedding under patch dropout: x (B, n_keep, C) holds the embeddings of patches
+    keep[b] ((B, n_keep) int32) of each image, slot (B, n) int32 is keep's inverse (patch_keep_indices).
+    Returns (B, n_keep + 1, C): the class token and every kept patch with its own position row.
+    The HIP kernels on the GPU; the same math in torch index ops elsewhere and for the widths the
+    kernels do not take (C no multiple of a 16-B vector)."""
+    if keep.dtype != torch.int32 or slot.dtype != torch.int32 or keep.shape != x.shape[:2] \
+            or slot.shape != (x.shape[0], pos.shape[1] - 1):
+        raise RuntimeError(f"token_embed_gather: keep (B, n_keep) / slot (B, n) int32 expected, got "
+                           f"{tuple(keep.shape)} {keep.dtype}, {tuple(slot.shape)} {slot.dtype}")
+    if _token_embed_vec_ok(x) and x.shape[1] >= 1:
+        return TokenEmbedGatherFn.apply(cls, x, pos, keep.contiguous(), slot.contiguous())
+    return _token_embed_gather_torch(cls, x, pos, keep)
 
 
 class AddPosFn(torch.autograd.Function):

@@ -265,6 +265,11 @@ class GraphedStep:
             # the mixup draws lam (and the lam > 0.5 text swap) on the host: a replay would repeat the
             # capture's draw forever
             raise ValueError("GraphedStep: balanced_mixup draws host-side randomness per step; run it eager")
+        visual = getattr(unwrap_model(model), "visual", None)
+        if hasattr(visual, "patch_dropout_active") and visual.patch_dropout_active():
+            # the step draws a fresh patch subset from torch's generator each time; how a capture replays
+            # that draw is the runtime's business, and this class does not change how captures replay
+            raise ValueError("GraphedStep: the visual tower's patch dropout draws randomness per step; run it eager")
         if concurrent and os.environ.get("GPU_MAX_HW_QUEUES", "").strip() == "1":
             # Capturing the towers' fork / join with both streams on one hardware queue ended the process
             # with SIGSEGV inside the HIP runtime's capture path (round 5); one hardware queue
@@ -311,7 +316,9 @@ def train_step_accum(model, batches, loss, optimizer, scaler, args, autocast=Non
     features as extra negatives.  A batch is (images, texts, targets) or, with
     balanced mixup, (images, texts, targets, balanced); the mixup is drawn in the
     caching pass (the reference re-draws it in the re-run too, from stale
-    balanced tensors: train.py:249-257).
+    balanced tensors: train.py:249-257).  With patch dropout on the visual tower each forward draws its
+    own patch subset: a fresh mask in the caching pass and another in the re-run, as open_clip's
+    accumulation does, so a micro-batch's cached image features and its re-run ones see different patches.
     """
     autocast = autocast or get_autocast(args.precision)
     cached = {}
