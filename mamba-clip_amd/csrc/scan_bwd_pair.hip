@@ -14,10 +14,15 @@
 // lane 2c + h keeps states [8h, 8h + 8) of channel c as 4 packed fp32 pairs, so every state-
 // position op is one v_pk_* for two states, and a wave is one workgroup's quarter (kQW waves share
 // the dB / dC reduction).  Per 32-position chunk (the forward's saved-state interval), in reverse:
-//  * B / C of the chunk: 16-bit rows read once per wave (one 16-B vector per lane and array),
-//    converted and laid out in LDS as {B_n, B_n+1, C_n, C_n+1} quads per (position, lane half, pair);
+//  * B / C of the chunk: 16-bit rows read once per workgroup (each wave a quarter of the positions),
+//    converted and laid out in LDS as {B_n, B_n+1, C_n, C_n+1} quads per (position, lane half, pair),
+//    one copy for the four waves, written one chunk ahead into the other of two buffers;
+//  * the u / delta / dout / z rows of the chunk: 32 rows x 64 B per array, copied to the wave's own
+//    LDS block by DMA one chunk ahead (scan_common.h: stage_src_elem), so that a row's line is
+//    fetched once per chunk and not once per sub-tile;
 //  * the per-position scalars dt = softplus(delta + bias), dt u, gy: each lane converts its 4
-//    positions of an 8-position sub-tile (8-B row loads), the pair partner's 4 arrive by DPP;
+//    positions of an 8-position sub-tile (8 B per array from the staged rows), the pair partner's
+//    4 arrive by DPP;
 //  * recompute pass: states at the sub-tile starts 8 / 16 / 24 from the saved chunk state (VGPRs);
 //  * sub-tiles in reverse, pairs one at a time: forward sweep (x_t, a_t in VGPRs), dC products,
 //    reverse adjoint sweep with packed S / Q / Y / dA accumulators, dB products; dB / dC are summed
@@ -146,10 +151,6 @@ __device__ __forceinline__ void glds16_asm(const void* gsrc, uint32_t m0v) {
                : "=&s"(keep) : "v"(gsrc), "s"(m0v) : "memory");
 }
 
-template <typename TI>
-__device__ __forceinline__ uint2 buf_ld8(__amdgpu_buffer_rsrc_t r, uint32_t off) {
-  return __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 0));
-}
 __device__ __forceinline__ void buf_st8(__amdgpu_buffer_rsrc_t r, uint32_t off, uint2 v) {
   typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
   __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_t, v), r, off, 0, 0);
@@ -170,9 +171,14 @@ __global__ __launch_bounds__(64 * kQW, 2) void scan_bwd_pair_kernel(const BwdPai
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  f32x4* bcq = reinterpret_cast<f32x4*>(smem) + wave * (kS * 2 * kQP);                    // [t][h][p]
-  float* dbc_base = reinterpret_cast<float*>(smem + (size_t)kQW * kS * 2 * kQP * 16);     // [buf][wave][t][2][16]
-  f32x4* xst = reinterpret_cast<f32x4*>(dbc_base + 2 * kQW * kDbcW) + wave * ((kQSub - 1) * 2 * 64);   // [s][2][lane]
+  static_assert(sizeof(TI) == 2 && kWV == 8 && kWL == 1, "16-bit rows: 8 positions per 16-B piece");
+  constexpr int kBcqQ = kS * 2 * kQP;          // B / C quads per chunk
+  f32x4* bcq_base = reinterpret_cast<f32x4*>(smem);                                       // [chunk & 1][t][h][p], one copy
+  float* dbc_base = reinterpret_cast<float*>(smem + (size_t)2 * kBcqQ * 16);              // [wave][t][2][16]
+  f32x4* xst = reinterpret_cast<f32x4*>(dbc_base + kQW * kDbcW) + wave * ((kQSub - 1) * 2 * 64);   // [s][2][lane]
+  // staged rows of the wave's chunk: [u, delta, dout, z][row][32 positions]
+  const char* stg = smem + (size_t)2 * kBcqQ * 16 + (size_t)kQW * kDbcW * 4 + (size_t)kQW * (kQSub - 1) * 2 * 64 * 16 +
+                    (size_t)wave * (4 * kStageArrayBytes);
 
   const int lin = xcd_remap(blockIdx.x, a.total_blocks);
   const int wblk = lin % a.nblk;
@@ -193,27 +199,31 @@ __global__ __launch_bounds__(64 * kQW, 2) void scan_bwd_pair_kernel(const BwdPai
     return make_rsrc(reinterpret_cast<const TI*>(base) + (int64_t)b * bs + (int64_t)dbase * ds,
                      nrows > 0 ? (uint32_t)(((int64_t)(nrows - 1) * ds + L_) * (int64_t)sizeof(TI)) : 0u);
   };
-  const __amdgpu_buffer_rsrc_t rs_u = rows_rsrc(a.u, a.u_bs, a.u_ds);
-  const __amdgpu_buffer_rsrc_t rs_d = rows_rsrc(a.delta, a.dt_bs, a.dt_ds);
-  const __amdgpu_buffer_rsrc_t rs_z = rows_rsrc(hasZ ? a.z : a.u, hasZ ? a.z_bs : a.u_bs, hasZ ? a.z_ds : a.u_ds);
-  const __amdgpu_buffer_rsrc_t rs_g = rows_rsrc(a.dout, a.go_bs, a.go_ds);
+  // input rows go to LDS by DMA (no range check: stage_src_elem keeps every source inside these rows)
+  auto rows_ptr = [&](const void* base, int64_t bs, int64_t ds) __attribute__((always_inline)) {
+    return reinterpret_cast<const TI*>(base) + (int64_t)b * bs + (int64_t)dbase * ds;
+  };
+  const TI* gb_u = rows_ptr(a.u, a.u_bs, a.u_ds);
+  const TI* gb_d = rows_ptr(a.delta, a.dt_bs, a.dt_ds);
+  const TI* gb_g = rows_ptr(a.dout, a.go_bs, a.go_ds);
+  const TI* gb_z = hasZ ? rows_ptr(a.z, a.z_bs, a.z_ds) : gb_u;
   const __amdgpu_buffer_rsrc_t rs_du = rows_rsrc(a.du, a.du_bs, a.du_ds);
   const __amdgpu_buffer_rsrc_t rs_dd = rows_rsrc(a.ddelta, a.ddt_bs, a.ddt_ds);
   const __amdgpu_buffer_rsrc_t rs_dz = rows_rsrc(hasZ ? a.dz : a.du, hasZ ? a.dz_bs : a.du_bs, hasZ ? a.dz_ds : a.du_ds);
   // element offsets of this lane's row; masked lanes write past every range (dropped)
-  const uint32_t ro_u = (uint32_t)(my_r * a.u_ds), ro_d = (uint32_t)(my_r * a.dt_ds);
-  const uint32_t ro_z = (uint32_t)(my_r * (hasZ ? a.z_ds : a.u_ds)), ro_g = (uint32_t)(my_r * a.go_ds);
   const uint32_t ro_du = (uint32_t)(my_r * a.du_ds), ro_dd = (uint32_t)(my_r * a.ddt_ds);
   const uint32_t ro_dz = (uint32_t)(my_r * (hasZ ? a.dz_ds : a.du_ds));
   const uint32_t st_mask = my_ok ? 0u : 0x80000000u;
 
-  // B / C rows of this (batch, group): lane j reads state row j >> 2, positions [8 (j & 3), +8) of a chunk
+  // B / C rows of this (batch, group), converted once per workgroup: wave w takes positions [8 w, 8 w + 8) of
+  // a chunk, its lane j state row j >> 2, positions 8 w + 2 (j & 3) and the next (one 4-B load per array)
   const __amdgpu_buffer_rsrc_t rs_B = make_rsrc(reinterpret_cast<const TW*>(a.B) + (int64_t)b * a.B_bs + (int64_t)g * a.B_gs,
                                                 (uint32_t)((15 * a.B_ns + L_) * (int64_t)sizeof(TW)));
   const __amdgpu_buffer_rsrc_t rs_C = make_rsrc(reinterpret_cast<const TW*>(a.C) + (int64_t)b * a.C_bs + (int64_t)g * a.C_gs,
                                                 (uint32_t)((15 * a.C_ns + L_) * (int64_t)sizeof(TW)));
-  const uint32_t bo_B = (uint32_t)(((lane >> 2) * a.B_ns + 8 * (lane & 3)) * (int64_t)sizeof(TW));
-  const uint32_t bo_C = (uint32_t)(((lane >> 2) * a.C_ns + 8 * (lane & 3)) * (int64_t)sizeof(TW));
+  const int bc_t0 = 8 * wave + 2 * (lane & 3);
+  const uint32_t bo_B = (uint32_t)(((lane >> 2) * a.B_ns + bc_t0) * (int64_t)sizeof(TW));
+  const uint32_t bo_C = (uint32_t)(((lane >> 2) * a.C_ns + bc_t0) * (int64_t)sizeof(TW));
   // saved chunk states of this wave's rows: [row][n_states][16]
   // saved states of this wave's rows: [b][row][n_states][16], or position-major [b][n_states][row][16] at the
   // fine interval (the forward's 32 rows of one position are then one contiguous 2 KB store)
@@ -236,31 +246,39 @@ __global__ __launch_bounds__(64 * kQW, 2) void scan_bwd_pair_kernel(const BwdPai
   const float biasv = a.delta_bias ? a.delta_bias[my_dc] : 0.f;
   float dDacc = 0.f, dbacc = 0.f;
 
-  // ---- software pipeline: B / C + chunk state of the next chunk; raw rows of the next sub-tile step
-  uint4 pB[kWL], pC[kWL];
+  // ---- software pipeline: B / C + chunk state of the next chunk (VGPRs), its rows (LDS DMA)
+  uint32_t pB, pC;
   f32x4 px[2];
   auto load_chunk = [&](int c) __attribute__((always_inline)) {   // c < 0: offsets out of range, reads 0
     const uint32_t lo = c >= 0 ? (uint32_t)(c * kS) * (uint32_t)sizeof(TW) : 0x80000000u;
-#pragma unroll
-    for (int k = 0; k < kWL; ++k) {
-      pB[k] = buf_ld16(rs_B, (bo_B + lo) + (uint32_t)(k * 16));
-      pC[k] = buf_ld16(rs_C, (bo_C + lo) + (uint32_t)(k * 16));
-    }
+    pB = __builtin_amdgcn_raw_buffer_load_b32(rs_B, bo_B + lo, 0, 0);
+    pC = __builtin_amdgcn_raw_buffer_load_b32(rs_C, bo_C + lo, 0, 0);
     // state after chunk c - 1 (zero for c == 0): floats [8h, 8h + 8) of my row
     const uint32_t ox = c > 0 ? ((uint32_t)my_r * cs_rs + (uint32_t)(c * (kFine ? kS / kQT : 1) - 1) * cs_ks + 8 * h) * 4u
                               : 0x80000000u;
     px[0] = __builtin_bit_cast(f32x4, buf_ld16(rs_cs, ox));
     px[1] = __builtin_bit_cast(f32x4, buf_ld16(rs_cs, ox + 16));
   };
-  uint2 nu, nd, nz, ng;   // raw rows (4 positions) of the next step
-  auto load_raw = [&](int pos) __attribute__((always_inline)) {   // pos: first position of the sub-tile
-    const uint32_t e = (uint32_t)(pos + 4 * h);
-    nu = buf_ld8<TI>(rs_u, (ro_u + e) * 2u);
-    nd = buf_ld8<TI>(rs_d, (ro_d + e) * 2u);
-    ng = buf_ld8<TI>(rs_g, (ro_g + e) * 2u);
-    if constexpr (hasZ) {
-      nz = buf_ld8<TI>(rs_z, (ro_z + e) * 2u);
+  // the loaded B / C pair of positions -> the quads of chunk c (all four waves fill one copy)
+  auto store_bc = [&](int c) __attribute__((always_inline)) {
+    const int n = lane >> 2;
+    float* dst = reinterpret_cast<float*>(bcq_base + (c & 1) * kBcqQ) + bc_t0 * (2 * kQP * 4) +
+                 ((n >> 3) * kQP + ((n & 7) >> 1)) * 4 + (n & 1);
+    const uint4 wB = make_uint4(pB, 0u, 0u, 0u), wC = make_uint4(pC, 0u, 0u, 0u);
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      dst[e * (2 * kQP * 4)] = elem_f<TW>(wB, e);
+      dst[e * (2 * kQP * 4) + 2] = elem_f<TW>(wC, e);
     }
+  };
+  // this lane's 4 positions of sub-tile s of the staged chunk (8 B per array)
+  const char* stg_lane = stg + stage_row_byte(ch, 4 * h);
+  auto read_rows = [&](int s, uint2& ru, uint2& rd, uint2& rz, uint2& rg) __attribute__((always_inline)) {
+    const char* p = stg_lane + s * (kQT * 2);
+    ru = *reinterpret_cast<const uint2*>(p);
+    rd = *reinterpret_cast<const uint2*>(p + kStageArrayBytes);
+    rg = *reinterpret_cast<const uint2*>(p + 2 * kStageArrayBytes);
+    rz = hasZ ? *reinterpret_cast<const uint2*>(p + 3 * kStageArrayBytes) : make_uint2(0u, 0u);
   };
 
   // per-position scalars of one sub-tile: this lane's 4 positions from its raw rows, the partner's by DPP
@@ -298,14 +316,13 @@ __global__ __launch_bounds__(64 * kQW, 2) void scan_bwd_pair_kernel(const BwdPai
     }
   };
   // B pair p / the {B, C} quad of pair p at chunk position t (LDS, two broadcast addresses per wave)
+  const f32x4* bcq = bcq_base;   // the current chunk's copy
   auto bpair = [&](int t, int p) __attribute__((always_inline)) -> f32x2 {
     return reinterpret_cast<const f32x2*>(bcq + t * (2 * kQP) + h * kQP + p)[0];
   };
   auto bquad = [&](int t, int p) __attribute__((always_inline)) -> f32x4 { return bcq[t * (2 * kQP) + h * kQP + p]; };
 
   const int nch = (L_ + kS - 1) / kS;
-  // raw rows walk: with recompute, the pass consumes sub-tiles 0 .. nsub - 2 forward and leaves the
-  // last sub-tile's rows in flight; with fine saved states the main loop starts there directly
   constexpr bool fine = kFine;
   // fine states: the entries of sub-tiles 1 .. 3 of chunk c (states after positions 32 c + 8 s + 7)
   // land in the sub-tile-entry slots by LDS DMA, issued one chunk ahead (after the previous chunk's
@@ -321,38 +338,44 @@ __global__ __launch_bounds__(64 * kQW, 2) void scan_bwd_pair_kernel(const BwdPai
       glds16_asm(src + 4, xst_lds + (uint32_t)(2 * s + 1) * 1024u);
     }
   };
-  if (fine) {
-    issue_fine(nch - 1);
-    __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
-  }
+  // rows: the u / delta / dout / z rows of chunk c land in the wave's own staging block by LDS DMA, all
+  // pieces of a row's line within one burst (the line is fetched once per chunk, not once per sub-tile).
+  // The block is single: the DMA of chunk c - 1 is issued in chunk c's last sub-tile (s = 0), once that
+  // sub-tile has its rows in registers, lands under its arithmetic and is waited for with the fine
+  // entries at the chunk start.  Only the issuing wave reads the block, so its vmcnt is all the ordering.
+  const uint32_t stg_lds = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_char_t*)(const_cast<char*>(stg)));
+  auto issue_rows = [&](int c) __attribute__((always_inline)) {
+    const int ol = opaque_lane_id();   // the addresses are rebuilt here, not kept in VGPRs across the sub-tiles
+    auto one = [&](const TI* gb, int64_t ds, int arr) __attribute__((always_inline)) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+        glds16_asm(gb + stage_src_elem(ol, i, c, nrows, L_, ds),
+                   stg_lds + (uint32_t)(arr * kStageArrayBytes) + stage_dst_byte(0, i));
+    };
+    one(gb_u, a.u_ds, 0);
+    one(gb_d, a.dt_ds, 1);
+    one(gb_g, a.go_ds, 2);
+    if constexpr (hasZ) one(gb_z, a.z_ds, 3);
+  };
+  issue_rows(nch - 1);
+  if (fine) issue_fine(nch - 1);
   load_chunk(nch - 1);
-  load_raw((nch - 1) * kS + (fine ? kQT * (min(kQSub, (L_ - (nch - 1) * kS) / kQT) - 1) : 0));
-  int buf = 0;
+  store_bc(nch - 1);
+  lds_barrier();   // the first chunk's quads are visible to every wave
+  float* dbc = dbc_base + wave * kDbcW;
   for (int c = nch - 1; c >= 0; --c) {
     const int l0 = c * kS;
     const int nsub = min(kQSub, (L_ - l0) / kQT);   // L % 8 == 0: whole sub-tiles
-    float* dbc = dbc_base + (buf * kQW + wave) * kDbcW;   // double-buffered: one barrier per chunk
+    bcq = bcq_base + (c & 1) * kBcqQ;
 
-    // ---- B / C of the chunk -> LDS quads; chunk-start state
-    {
-      const int n = lane >> 2, q = lane & 3;
-      float* dst = reinterpret_cast<float*>(bcq) + ((n >> 3) * kQP + ((n & 7) >> 1)) * 4 + (n & 1);
-#pragma unroll
-      for (int k = 0; k < kWL; ++k)
-#pragma unroll
-        for (int e = 0; e < kWV; ++e) {
-          const int t = 8 * q + k * kWV + e;
-          dst[t * (2 * kQP * 4)] = elem_f<TW>(pB[k], e);
-          dst[t * (2 * kQP * 4) + 2] = elem_f<TW>(pC[k], e);
-        }
-    }
+    // ---- chunk-start state
     f32x2 x0[kQP];
     x0[0] = px[0].lo; x0[1] = px[0].hi; x0[2] = px[1].lo; x0[3] = px[1].hi;
     if (!my_ok) {
 #pragma unroll
       for (int p = 0; p < kQP; ++p) x0[p] = f32x2{0.f, 0.f};
     }
-    if (fine) __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): the DMA of this chunk's entries landed
+    __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): the DMA of this chunk's rows and entries landed
     load_chunk(c - 1);
     wave_lds_sync();
 
@@ -365,8 +388,8 @@ __global__ __launch_bounds__(64 * kQW, 2) void scan_bwd_pair_kernel(const BwdPai
       for (int p = 0; p < kQP; ++p) x[p] = x0[p];
 #pragma unroll 1
       for (int s = 0; s + 1 < nsub; ++s) {
-        const uint2 ru = nu, rd = nd, rz = nz, rg = ng;
-        load_raw(l0 + kQT * (s + 1));
+        uint2 ru, rd, rz, rg;
+        read_rows(s, ru, rd, rz, rg);
         Sc sc;
         scalars(ru, rd, rz, rg, false, sc);
         // x = a x + B dt u: the product with B off the state chain (one pk_fma per step on it)
@@ -385,14 +408,17 @@ __global__ __launch_bounds__(64 * kQW, 2) void scan_bwd_pair_kernel(const BwdPai
         xst[(2 * s + 1) * 64 + lane] = f32x4{x[2].x, x[2].y, x[3].x, x[3].y};
       }
     }
-    wave_lds_sync();
+    lds_barrier();   // the previous chunk's dB / dC partials are summed: the (single) buffer is free
 
     // ---- sub-tiles in reverse
 #pragma unroll 1
     for (int s = nsub - 1; s >= 0; --s) {
-      const uint2 ru = nu, rd = nd, rz = nz, rg = ng;
-      // next step; after s = 0 the next chunk's first step (full chunk: its last sub-tile when fine)
-      load_raw(s > 0 ? l0 + kQT * (s - 1) : (fine ? l0 - kQT : l0 - kS));
+      uint2 ru, rd, rz, rg;
+      read_rows(s, ru, rd, rz, rg);
+      if (s == 0 && c > 0) {   // every slot of the block is consumed: fetch the next chunk's rows
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        issue_rows(c - 1);
+      }
       Sc sc;
       scalars(ru, rd, rz, rg, true, sc);
       // state entering the sub-tile: the chunk start (registers) or the recompute pass's (LDS)
@@ -526,12 +552,13 @@ __global__ __launch_bounds__(64 * kQW, 2) void scan_bwd_pair_kernel(const BwdPai
         buf_st8(rs_dz, ((ro_dz + e0) * 2u) | st_mask, make_uint2(cvt_pk2<TI>(o_dz[0], o_dz[1]), cvt_pk2<TI>(o_dz[2], o_dz[3])));
     }
 
+    if (c > 0) store_bc(c - 1);             // this wave's quarter of the next chunk's quads (the other copy)
     if (fine && c > 0) issue_fine(c - 1);   // the slots are free: this chunk's sub-tiles are done
     // ---- dB / dC of the chunk: sum over the workgroup's waves (fixed order) -> slab
     lds_barrier();
     {
       float* slab = a.slab_bc + (((int64_t)bg * a.nblk + wblk) * L_ + l0) * (2 * kQN);
-      const float* src = dbc_base + buf * kQW * kDbcW;
+      const float* src = dbc_base;
       for (int f = tid; f < kDbcW / 4; f += 64 * kQW) {
         f32x4 acc = reinterpret_cast<const f32x4*>(src)[f];
 #pragma unroll
@@ -539,7 +566,6 @@ __global__ __launch_bounds__(64 * kQW, 2) void scan_bwd_pair_kernel(const BwdPai
         if (4 * f < (L_ - l0) * 2 * kQN) reinterpret_cast<f32x4*>(slab)[f] = acc;
       }
     }
-    buf ^= 1;   // the next barrier orders this chunk's reads before the buffer is written again
   }
 
   // ---- per-channel parameter gradients
@@ -558,10 +584,14 @@ __global__ __launch_bounds__(64 * kQW, 2) void scan_bwd_pair_kernel(const BwdPai
   }
 }
 
-// B / C quads, dB / dC partials (double-buffered), sub-tile states: 72 KB, two workgroups per CU
+// B / C quads (one copy, double-buffered: 8 KB), dB / dC partials (16 KB), sub-tile states (24 KB), staged rows
+// (32 KB): 80 KB, two workgroups per CU
 size_t bwd_pair_lds_bytes() {
-  return (size_t)kQW * kS * 2 * kQP * 16 + (size_t)2 * kQW * kS * 2 * kQN * 4 + (size_t)kQW * (kQSub - 1) * 2 * 64 * 16;
+  return (size_t)2 * kS * 2 * kQP * 16 + (size_t)kQW * kS * 2 * kQN * 4 + (size_t)kQW * (kQSub - 1) * 2 * 64 * 16 +
+         (size_t)kQW * 4 * kStageArrayBytes;
 }
+static_assert(2 * (2 * kS * 2 * kQP * 16 + kQW * kS * 2 * kQN * 4 + kQW * (kQSub - 1) * 2 * 64 * 16 + kQW * 4 * kStageArrayBytes) <=
+              160 * 1024, "two workgroups per CU");
 int bwd_pair_nblk(int H) { return (H + kQCh * kQW - 1) / (kQCh * kQW); }
 
 // Eligibility (the host has validated shapes; strides in elements).

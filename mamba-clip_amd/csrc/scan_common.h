@@ -99,6 +99,26 @@ __device__ __forceinline__ f32x2 hi_to_lo(f32x2 s) {   // {s.hi, unspecified}: o
   return r;
 }
 
+// Row staging of the pair backward (scan_bwd_pair.hip).  Per 32-position chunk a wave copies 32 rows x
+// 64 B of one 16-bit array to LDS with two 64-lane LDS-DMA instructions of 16 B per lane: lane `lane`
+// of instruction `i` takes row 16 i + lane / 4, 16-B piece lane % 4 (8 positions), and the hardware
+// puts it at m0 + 16 lane, i.e. the block is [row][64 B].  The DMA checks no range, so a row past
+// `nrows` (a wave without rows keeps its anchor row) and a piece past the sequence end are clamped to
+// the last valid row / piece of the same array; what they fetch is never used.  Host-callable so that
+// the offsets can be checked without a GPU.
+constexpr int kStageRowBytes = kS * 2;                  // one staged row: 32 positions, 16 bit
+constexpr int kStageInstrBytes = 64 * 16;               // one DMA instruction: 16 rows
+constexpr int kStageArrayBytes = 32 * kStageRowBytes;   // one array of a wave
+// element offset of the piece's source from the wave's first row (seqlen % 8 == 0, seqlen >= 8)
+__host__ __device__ inline int64_t stage_src_elem(int lane, int i, int chunk, int nrows, int seqlen, int64_t row_stride) {
+  const int last_row = nrows > 0 ? nrows - 1 : 0;
+  const int row = 16 * i + (lane >> 2), pos = chunk * kS + 8 * (lane & 3);
+  return (int64_t)(row < last_row ? row : last_row) * row_stride + (pos < seqlen - 8 ? pos : seqlen - 8);
+}
+// LDS byte of (row, chunk position) in a staged array, and where lane `lane` of instruction `i` lands
+__host__ __device__ inline uint32_t stage_row_byte(int row, int pos) { return (uint32_t)(row * kStageRowBytes + pos * 2); }
+__host__ __device__ inline uint32_t stage_dst_byte(int lane, int i) { return (uint32_t)(i * kStageInstrBytes + lane * 16); }
+
 // Forward kernel arguments (scan_fwd.hip, scan_fwd_pair.hip).
 struct FwdArgs {
   int batch, dim, seqlen, dstate, n_groups, n_chunks, n_states, nblk, total_blocks;

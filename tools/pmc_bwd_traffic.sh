@@ -1,13 +1,13 @@
 #!/bin/bash
 # HBM traffic and L2 hit rate of the scan backward at one shape (run on the GPU box).
-#   usage: tools/pmc_bwd_traffic.sh <outdir> <shape>
+#   usage: tools/pmc_bwd_traffic.sh <outdir> <shape> [extra time_scan.py flags, e.g. --cm]
 set -u
-out=$1; shp=$2; mkdir -p "$out"
+out=$1; shp=$2; extra=${3:-}; mkdir -p "$out"
 export TMPDIR=/tmp
 for pass in FETCH_SIZE WRITE_SIZE "TCC_HIT_sum TCC_MISS_sum"; do
   tag=$(echo $pass | cut -d' ' -f1)
   timeout -s KILL 120 rocprofv3 --pmc $pass -d "$out/$tag" -o p --output-format csv \
-    -- python tools/time_scan.py --shape $shp --iters 3 --bwd > "$out/$tag.log" 2>&1 || { echo "pass $tag failed"; exit 1; }
+    -- python tools/time_scan.py --shape $shp --iters 3 --bwd $extra > "$out/$tag.log" 2>&1 || { echo "pass $tag failed"; exit 1; }
 done
 python - "$out" <<'PY'
 import csv, glob, sys, collections
