@@ -6,6 +6,9 @@
  * torch's scaled_dot_product_attention (model.py:1019-1064 builds
  * the towers); it replaces that call for the unmasked, dropout-free case:
  *   o = softmax(scale * q k^T) v          per (batch, head)
+ * Two variants of the same kernels follow below: with a key-padding mask (mc_attn_masked_*: the
+ * BERT text tower's padded captions) and with the causal mask (mc_attn_causal_*: the CLIP text
+ * transformer, 77 tokens).
  * One workgroup owns one (batch, head): the whole sequence's K / V (and, backward, Q / dO)
  * sit in LDS, so the softmax is exact in one pass (no online rescaling) and dQ / dK / dV
  * need no cross-workgroup sums.
@@ -17,7 +20,7 @@
  * 16-B aligned rows (pointers and the three strides multiples of 8 elements).
  * Batch and head strides are 64-bit and free (any sign, any size).  Token strides are not: the
  * kernels read K / V (every kernel) and, backward at seqlen > 224, Q / dO / O through 32-bit
- * buffer byte offsets, so q_ns (all four entry points) and o_ns (the two backward ones) must be
+ * buffer byte offsets, so q_ns (every entry point) and o_ns (the backward ones) must be
  * >= 0 with ((seqlen - 1) * ns + 64) * 2 bytes <= 2^31 -- at seqlen 256 ns <= 4210752 elements;
  * anything else returns MC_ERR_SHAPE before a launch.  (o_ns of the forward and dq_ns are only
  * written through, with 64-bit addresses: no limit.)
@@ -111,6 +114,21 @@ typedef struct {
 } mc_attn_masked_bwd_params;
 
 int mc_attn_masked_bwd(const mc_attn_masked_bwd_params* p, void* stream);
+
+/*
+ * Causal variant (the CLIP text transformer: 77 tokens, pooled at the end-of-text token):
+ *   o = softmax(scale * q k^T + (j <= i ? 0 : -inf)) v
+ * Query i attends to the keys j <= i; lse is over those keys; dq / dk / dv / dsum are the
+ * gradients of that.  The parameter structs, requirements, token-stride limits and return codes
+ * are those of mc_attn_fwd / mc_attn_bwd.  32-key tiles above the diagonal are never visited, tiles
+ * below it run the unmasked instructions, the diagonal tile pays one select per score.  Every query
+ * has itself as a key, so no row is empty; row i of o, lse and dq depends on rows <= i of the
+ * inputs only, bit for bit.  Query 0 has one key: its dS is stored as the exact zero it is.
+ * Bitwise reproducible (no atomics).  Not combined with the key-padding mask: with end-of-text
+ * pooling the tokens after it cannot reach the pooled row.
+ */
+int mc_attn_causal_fwd(const mc_attn_fwd_params* p, void* stream);
+int mc_attn_causal_bwd(const mc_attn_bwd_params* p, void* stream);
 
 #ifdef __cplusplus
 }

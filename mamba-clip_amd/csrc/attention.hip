@@ -28,6 +28,17 @@
 // keys < N) live in one VGPR, word t on lane t, and come out wave-uniform through v_readlane: a
 // tile whose word is 0 is skipped by a scalar branch, a tile whose word is all ones takes the
 // unmasked instructions, only a mixed tile pays the per-key selects.
+//
+// Causal variant (mc_attn_causal_fwd / _bwd, the CLIP text transformer: 77 tokens, pooled at the
+// end-of-text token): a third instantiation, kCausal = true, every added instruction under
+// `if constexpr (kCausal)`; same argument structs as the unmasked kernels.  Query i sees keys j <= i.
+// The 32 x 32 tiles already fit: a tile below the diagonal (key tile < query block) takes the
+// unmasked instructions, a tile above it is never visited (the sweeps end / start at the diagonal,
+// wave-uniform bounds), and only the diagonal tile pays one select per score: -1e30 above the
+// diagonal in both forward passes, P = dS = 0 there in the backward (selects, so an overflowed P
+// cannot leave a NaN).  Keys past N lie above the diagonal of every stored query, so the ragged last
+// tile needs no test of its own.  Query 0 sees key 0 alone: P = 1 and dS = 0 exactly, and the
+// backward stores that zero instead of the rounding residue of dP - delta.
 #include <algorithm>
 #include <type_traits>
 
@@ -202,7 +213,7 @@ __device__ __forceinline__ uint32_t word_of(uint32_t wv, int t) {
 // accumulator register r holds row (r & 3) + 8 (r >> 2) + 4 hh of its tile: bit of that row in wl = w >> 4 hh
 __device__ __forceinline__ bool row_bit(uint32_t wl, int r) { return (wl >> ((r & 3) + 8 * (r >> 2))) & 1u; }
 
-template <typename TI, int NT, bool kMask = false>
+template <typename TI, int NT, bool kMask = false, bool kCausal = false>
 __global__ __launch_bounds__(64 * kFwdWaves, 2) void attn_fwd_kernel(const typename ArgsOf<kMask, FwdArgs, FwdArgsM>::type a) {
   using M = M32<TI>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -233,6 +244,8 @@ __global__ __launch_bounds__(64 * kFwdWaves, 2) void attn_fwd_kernel(const typen
   // this wave's 32-query block (B operand: lane = query, 16-B chunks 2 s + hh of its row)
   const int qt = wave;
   const int q = qt * 32 + l32;
+  int tEnd = NT;   // kCausal: the key tiles up to the diagonal one (wave-uniform)
+  if constexpr (kCausal) tEnd = __builtin_amdgcn_readfirstlane(qt) + 1;
   uint4 qf[4];
   {
     const TI* qrow = qg + (int64_t)min(q, N - 1) * a.q_ns;
@@ -256,6 +269,8 @@ __global__ __launch_bounds__(64 * kFwdWaves, 2) void attn_fwd_kernel(const typen
     // S costs 4 MFMAs per tile and keeps one tile of scores live instead of all NT (no spills).
     // kMask: w = the tile's mask word (keys >= N already cleared); masked keys score -1e30 like
     // the keys past N, so their probabilities are exactly 0.
+    // kCausal: the diagonal tile t == qt scores -1e30 where key > query (that covers the keys past N
+    // of every stored query); both passes go through here, so both make the comparison.
     auto s_tile = [&](int t, uint32_t w) __attribute__((always_inline)) {
       f32x16 acc = {};
 #pragma unroll
@@ -267,6 +282,12 @@ __global__ __launch_bounds__(64 * kFwdWaves, 2) void attn_fwd_kernel(const typen
           for (int r = 0; r < 16; ++r)
             if (!row_bit(wl, r)) acc[r] = -1e30f;
         }
+      } else if constexpr (kCausal) {
+        if (t == tEnd - 1) {   // wave-uniform
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if ((r & 3) + 8 * (r >> 2) + 4 * hh > l32) acc[r] = -1e30f;
+        }
       } else if (t == NT - 1 && Np > N) {   // keys past N (last tile only)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
@@ -276,7 +297,7 @@ __global__ __launch_bounds__(64 * kFwdWaves, 2) void attn_fwd_kernel(const typen
     };
     float m = -1e30f;
 #pragma unroll 1
-    for (int t = 0; t < NT; ++t) {
+    for (int t = 0; t < tEnd; ++t) {
       uint32_t w = 0;
       if constexpr (kMask) {
         w = word_of(wv, t);
@@ -292,7 +313,7 @@ __global__ __launch_bounds__(64 * kFwdWaves, 2) void attn_fwd_kernel(const typen
     float l = 0.f;
     f32x16 o0 = {}, o1 = {};
 #pragma unroll 1
-    for (int t = 0; t < NT; ++t) {
+    for (int t = 0; t < tEnd; ++t) {
       uint32_t w = 0;
       if constexpr (kMask) {
         w = word_of(wv, t);
@@ -341,7 +362,7 @@ struct BwdArgs {
 };
 struct BwdArgsM : BwdArgs { const uint32_t* mask; };
 
-template <typename TI, int NT, bool kMask = false>
+template <typename TI, int NT, bool kMask = false, bool kCausal = false>
 __global__ __launch_bounds__(64 * kBwdWaves, 1) void attn_bwd_kernel(const typename ArgsOf<kMask, BwdArgs, BwdArgsM>::type a) {
   using M = M32<TI>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -497,8 +518,13 @@ __global__ __launch_bounds__(64 * kBwdWaves, 1) void attn_bwd_kernel(const typen
     // overflowed P of a masked key cannot leave a NaN), and a tile without a valid key skips the sweep.
     uint32_t kw = 0xFFFFFFFFu;
     if constexpr (kMask) kw = word_of(wv, kt);
+    // kCausal: the query blocks from the diagonal one on; in the diagonal block P = dS = 0 where
+    // query < key (selects: an overflowed P above the diagonal cannot leave a NaN), and dS of query 0
+    // (one key: P = 1, dS = 0 exactly) is stored as that zero.
+    int qt0 = 0;
+    if constexpr (kCausal) qt0 = __builtin_amdgcn_readfirstlane(kt);
 #pragma unroll 1
-    for (int qt = 0; qt < (kw != 0 ? NT : 0); ++qt) {
+    for (int qt = qt0; qt < (kw != 0 ? NT : 0); ++qt) {
       f32x16 sa = {}, pa = {};
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
@@ -515,6 +541,17 @@ __global__ __launch_bounds__(64 * kBwdWaves, 1) void attn_bwd_kernel(const typen
           const float p = fast_exp2(sa[4 * j + i] * a.c2 - L[i]);
           sa[4 * j + i] = p;
           pa[4 * j + i] = p * (pa[4 * j + i] - Dl[i]);
+        }
+      }
+      if constexpr (kCausal) {
+        if (qt == qt0) {   // wave-uniform
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const bool above = 8 * (r >> 2) + 4 * hh + (r & 3) < l32;
+            if (above) sa[r] = 0.f;
+            if (above) pa[r] = 0.f;
+          }
+          if (qt0 == 0 && hh == 0) pa[0] = 0.f;   // query 0
         }
       }
 #pragma unroll
@@ -556,8 +593,10 @@ __global__ __launch_bounds__(64 * kBwdWaves, 1) void attn_bwd_kernel(const typen
   }
   if (wave < NT) {
     f32x16 dq0 = {}, dq1 = {};
+    int ktEnd = NT;   // kCausal: the key tiles up to the diagonal one
+    if constexpr (kCausal) ktEnd = __builtin_amdgcn_readfirstlane(qt) + 1;
 #pragma unroll 1
-    for (int kt = 0; kt < NT; ++kt) {
+    for (int kt = 0; kt < ktEnd; ++kt) {
       uint32_t w = 0;
       if constexpr (kMask) {
         w = word_of(wv, kt);
@@ -580,6 +619,14 @@ __global__ __launch_bounds__(64 * kBwdWaves, 1) void attn_bwd_kernel(const typen
 #pragma unroll
           for (int r = 0; r < 16; ++r)
             if (!row_bit(wl, r)) pa[r] = 0.f;
+        }
+      }
+      if constexpr (kCausal) {
+        if (kt == ktEnd - 1) {   // diagonal tile: keys on the accumulator rows; query 0 has dS = 0
+          const bool q0 = q == 0;
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if ((r & 3) + 8 * (r >> 2) + 4 * hh > l32 || q0) pa[r] = 0.f;
         }
       }
 #pragma unroll
@@ -623,43 +670,44 @@ static int num_cus() {
   return n;
 }
 
-// A = FwdArgs / BwdArgs: the unmasked kernels; A = FwdArgsM / BwdArgsM: the kMask instantiations
-template <typename TI, int NT, typename A>
+// A = FwdArgs / BwdArgs: the unmasked kernels, or with kCausal the causal ones; A = FwdArgsM /
+// BwdArgsM: the kMask instantiations
+template <typename TI, int NT, bool kCausal, typename A>
 void launch_fwd_nt(const A& a, hipStream_t s) {
   constexpr bool kMask = std::is_same<A, FwdArgsM>::value;
-  hipLaunchKernelGGL((attn_fwd_kernel<TI, NT, kMask>), dim3(a.B * a.H), dim3(64 * kFwdWaves), fwd_lds(NT), s, a);
+  hipLaunchKernelGGL((attn_fwd_kernel<TI, NT, kMask, kCausal>), dim3(a.B * a.H), dim3(64 * kFwdWaves), fwd_lds(NT), s, a);
 }
-template <typename TI, int NT, typename A>
+template <typename TI, int NT, bool kCausal, typename A>
 void launch_bwd_nt(const A& a, hipStream_t s) {
   constexpr bool kMask = std::is_same<A, BwdArgsM>::value;
   // NT <= 7: persistent, one workgroup per CU walks the heads (the LDS of one head fills the CU)
   const int grid = NT <= 7 ? std::min(a.B * a.H, num_cus()) : a.B * a.H;
-  hipLaunchKernelGGL((attn_bwd_kernel<TI, NT, kMask>), dim3(grid), dim3(64 * kBwdWaves), bwd_lds(NT), s, a);
+  hipLaunchKernelGGL((attn_bwd_kernel<TI, NT, kMask, kCausal>), dim3(grid), dim3(64 * kBwdWaves), bwd_lds(NT), s, a);
 }
-template <typename TI, typename A>
+template <typename TI, bool kCausal, typename A>
 void launch_fwd(const A& a, hipStream_t s) {
   switch ((a.N + 31) / 32) {
-    case 1: launch_fwd_nt<TI, 1>(a, s); break;
-    case 2: launch_fwd_nt<TI, 2>(a, s); break;
-    case 3: launch_fwd_nt<TI, 3>(a, s); break;
-    case 4: launch_fwd_nt<TI, 4>(a, s); break;
-    case 5: launch_fwd_nt<TI, 5>(a, s); break;
-    case 6: launch_fwd_nt<TI, 6>(a, s); break;
-    case 7: launch_fwd_nt<TI, 7>(a, s); break;
-    default: launch_fwd_nt<TI, 8>(a, s); break;
+    case 1: launch_fwd_nt<TI, 1, kCausal>(a, s); break;
+    case 2: launch_fwd_nt<TI, 2, kCausal>(a, s); break;
+    case 3: launch_fwd_nt<TI, 3, kCausal>(a, s); break;
+    case 4: launch_fwd_nt<TI, 4, kCausal>(a, s); break;
+    case 5: launch_fwd_nt<TI, 5, kCausal>(a, s); break;
+    case 6: launch_fwd_nt<TI, 6, kCausal>(a, s); break;
+    case 7: launch_fwd_nt<TI, 7, kCausal>(a, s); break;
+    default: launch_fwd_nt<TI, 8, kCausal>(a, s); break;
   }
 }
-template <typename TI, typename A>
+template <typename TI, bool kCausal, typename A>
 void launch_bwd(const A& a, hipStream_t s) {
   switch ((a.N + 31) / 32) {
-    case 1: launch_bwd_nt<TI, 1>(a, s); break;
-    case 2: launch_bwd_nt<TI, 2>(a, s); break;
-    case 3: launch_bwd_nt<TI, 3>(a, s); break;
-    case 4: launch_bwd_nt<TI, 4>(a, s); break;
-    case 5: launch_bwd_nt<TI, 5>(a, s); break;
-    case 6: launch_bwd_nt<TI, 6>(a, s); break;
-    case 7: launch_bwd_nt<TI, 7>(a, s); break;
-    default: launch_bwd_nt<TI, 8>(a, s); break;
+    case 1: launch_bwd_nt<TI, 1, kCausal>(a, s); break;
+    case 2: launch_bwd_nt<TI, 2, kCausal>(a, s); break;
+    case 3: launch_bwd_nt<TI, 3, kCausal>(a, s); break;
+    case 4: launch_bwd_nt<TI, 4, kCausal>(a, s); break;
+    case 5: launch_bwd_nt<TI, 5, kCausal>(a, s); break;
+    case 6: launch_bwd_nt<TI, 6, kCausal>(a, s); break;
+    case 7: launch_bwd_nt<TI, 7, kCausal>(a, s); break;
+    default: launch_bwd_nt<TI, 8, kCausal>(a, s); break;
   }
 }
 
@@ -690,8 +738,8 @@ static int check_token_stride(int64_t ns, int N, const char* who, const char* na
 
 using namespace mc;
 
-// Shared by the unmasked and the masked entry points (P: the parameter struct, A: FwdArgs[M] / BwdArgs[M])
-template <typename P, typename A>
+// Shared by the unmasked, the masked and the causal entry points (P: the parameter struct, A: FwdArgs[M] / BwdArgs[M])
+template <bool kCausal = false, typename P, typename A>
 static int run_fwd(const P* p, A& a, void* stream, const char* who) {
   MC_CHECK(p, MC_ERR_INVALID, "%s: null params", who);
   const int rc = attn::check_common(p->batch, p->heads, p->seqlen, p->head_dim, p->dtype, who);
@@ -711,14 +759,14 @@ static int run_fwd(const P* p, A& a, void* stream, const char* who) {
   a.q_bs = p->q_bs; a.q_ns = p->q_ns; a.q_hs = p->q_hs;
   a.o = p->o; a.o_bs = p->o_bs; a.o_ns = p->o_ns; a.o_hs = p->o_hs;
   a.lse = p->lse;
-  if (p->dtype == MC_DTYPE_BF16) attn::launch_fwd<bf16_t>(a, (hipStream_t)stream);
-  else attn::launch_fwd<f16_t>(a, (hipStream_t)stream);
+  if (p->dtype == MC_DTYPE_BF16) attn::launch_fwd<bf16_t, kCausal>(a, (hipStream_t)stream);
+  else attn::launch_fwd<f16_t, kCausal>(a, (hipStream_t)stream);
   const hipError_t e = hipGetLastError();
   MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e));
   return MC_OK;
 }
 
-template <typename P, typename A>
+template <bool kCausal = false, typename P, typename A>
 static int run_bwd(const P* p, A& a, void* stream, const char* who) {
   MC_CHECK(p, MC_ERR_INVALID, "%s: null params", who);
   const int rc = attn::check_common(p->batch, p->heads, p->seqlen, p->head_dim, p->dtype, who);
@@ -745,8 +793,8 @@ static int run_bwd(const P* p, A& a, void* stream, const char* who) {
   a.dq = p->dq; a.dk = p->dk; a.dv = p->dv;
   a.d_bs = p->dq_bs; a.d_ns = p->dq_ns; a.d_hs = p->dq_hs;
   a.dsum = p->dsum;
-  if (p->dtype == MC_DTYPE_BF16) attn::launch_bwd<bf16_t>(a, (hipStream_t)stream);
-  else attn::launch_bwd<f16_t>(a, (hipStream_t)stream);
+  if (p->dtype == MC_DTYPE_BF16) attn::launch_bwd<bf16_t, kCausal>(a, (hipStream_t)stream);
+  else attn::launch_bwd<f16_t, kCausal>(a, (hipStream_t)stream);
   const hipError_t e = hipGetLastError();
   MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e));
   return MC_OK;
@@ -767,4 +815,12 @@ extern "C" int mc_attn_masked_fwd(const mc_attn_masked_fwd_params* p, void* stre
 extern "C" int mc_attn_masked_bwd(const mc_attn_masked_bwd_params* p, void* stream) {
   attn::BwdArgsM a;
   return run_bwd(p, a, stream, "mc_attn_masked_bwd");
+}
+extern "C" int mc_attn_causal_fwd(const mc_attn_fwd_params* p, void* stream) {
+  attn::FwdArgs a;
+  return run_fwd<true>(p, a, stream, "mc_attn_causal_fwd");
+}
+extern "C" int mc_attn_causal_bwd(const mc_attn_bwd_params* p, void* stream) {
+  attn::BwdArgs a;
+  return run_bwd<true>(p, a, stream, "mc_attn_causal_bwd");
 }

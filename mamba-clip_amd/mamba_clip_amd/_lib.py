@@ -344,6 +344,8 @@ SYMBOLS = {
     "mc_attn_bwd": (ctypes.c_int, [ctypes.POINTER(AttnBwdParams), c_vp]),
     "mc_attn_masked_fwd": (ctypes.c_int, [ctypes.POINTER(AttnMaskedFwdParams), c_vp]),
     "mc_attn_masked_bwd": (ctypes.c_int, [ctypes.POINTER(AttnMaskedBwdParams), c_vp]),
+    "mc_attn_causal_fwd": (ctypes.c_int, [ctypes.POINTER(AttnFwdParams), c_vp]),
+    "mc_attn_causal_bwd": (ctypes.c_int, [ctypes.POINTER(AttnBwdParams), c_vp]),
     "mc_patch_embed_input": (ctypes.c_int, [ctypes.POINTER(PatchInputParams), c_vp]),
     "mc_patch_embed_input_gather": (ctypes.c_int, [ctypes.POINTER(PatchInputParams), c_vp, c_i32, c_vp]),
     "mc_token_embed_gather_fwd": (ctypes.c_int, [ctypes.POINTER(TokenEmbedGatherParams), c_vp]),

@@ -55,7 +55,8 @@ def build_parser():
                    help="stage-1 model config (offline: vit_b16-mamba130m, tiny-mamba-clip, mamba790m-text, "
                         "biomedclip-vit_b16-pubmedbert256, biomedclip-vit_b16-pubmedbert256-hf: the text "
                         "tower that computes HF BertModel, vit_b16-mamba130m-hf: the Mamba tower pooled at each "
-                        "caption's last non-pad token, HF MambaModel)")
+                        "caption's last non-pad token, HF MambaModel, clip-vit_b16-hf: the CLIP vision tower with the "
+                        "causal CLIP text transformer, HF CLIPModel)")
     p.add_argument("--model-stage-1", type=str, default=None, help="alias of --model for stage 2")
     p.add_argument("--model-stage-2", type=str, default="ClipClassifier")
     p.add_argument("--use-inner-prod", action="store_true")

@@ -18,6 +18,8 @@ SURVEY.md 8c) are defined here and random-initialised:
                      pools each caption's last token and computes transformers.MambaModel
   BertTextEncoder    PubMedBERT-base shape (12 x 768, ctx 256) for BiomedCLIP
   HFBertTextEncoder  the same tower computing transformers.BertModel (post-LN, token types, padding mask)
+  ClipTextEncoder    the CLIP text transformer (12 x 512, 77 tokens, causal attention, end-of-text
+                     pooling) computing transformers.CLIPTextModelWithProjection
 Hot ops run on the HIP library: selective scan, causal conv1d, fused
 add+RMSNorm / add+LayerNorm, patch im2col, short-sequence attention
 (attention.hip), contrastive loss; dense projections are plain library GEMMs
@@ -304,9 +306,13 @@ def _gpu_sdpa_backends():
 
 
 class Attention(nn.Module):
-    def __init__(self, dim, heads):
+    """causal=True: query i attends to the keys j <= i (the CLIP text transformer): the fused path runs
+    mc_attn_causal_fwd / _bwd, the fallback SDPA with is_causal=True; not combined with a padding mask."""
+
+    def __init__(self, dim, heads, causal=False):
         super().__init__()
         self.heads = heads
+        self.causal = bool(causal)
         self.qkv = nn.Linear(dim, 3 * dim, bias=True)
         self.proj = nn.Linear(dim, dim)
         self.fused_attention = True   # mc_attn_fwd/bwd where supported (bf16/f16, head_dim 64, N <= 256)
@@ -320,6 +326,8 @@ class Attention(nn.Module):
         Bsz, N, C = x.shape
         if valid is None and key_mask is not None:
             raise ValueError("Attention: key_mask needs the boolean `valid` it was packed from")
+        if self.causal and valid is not None:
+            raise ValueError("Attention: causal attention takes no key-padding mask")
         if self.fused_attention and x.is_cuda and attn_supported(N, C // self.heads, _compute_dtype(x)):
             # packed qkv projection -> fused attention kernel (ops.PackedAttentionFn: the whole
             # sequence of a head in LDS) -> output projection; o is already (B, N, C) and the
@@ -328,6 +336,8 @@ class Attention(nn.Module):
             qkv = linear_sk(x, self.qkv.weight, self.qkv.bias)
             if valid is not None and key_mask is None:
                 key_mask = pack_key_mask(valid)
+            if self.causal:
+                return linear_sk(packed_attention(qkv, self.heads, causal=True), self.proj.weight, self.proj.bias)
             return linear_sk(packed_attention(qkv, self.heads, key_mask), self.proj.weight, self.proj.bias)
         self.last_path = "sdpa"
         # unbind (not index) the q/k/v slices: its backward stacks the three
@@ -339,9 +349,9 @@ class Attention(nn.Module):
         am = valid[:, None, None, :] if valid is not None else None   # True = attend
         if x.is_cuda:
             with _gpu_sdpa_backends():
-                o = F.scaled_dot_product_attention(q, k, v, attn_mask=am)
+                o = F.scaled_dot_product_attention(q, k, v, attn_mask=am, is_causal=self.causal)
         else:
-            o = F.scaled_dot_product_attention(q, k, v, attn_mask=am)
+            o = F.scaled_dot_product_attention(q, k, v, attn_mask=am, is_causal=self.causal)
         return linear_sk(o.transpose(1, 2).reshape(Bsz, N, C), self.proj.weight, self.proj.bias)
 
 
@@ -353,13 +363,20 @@ class ViTBlock(nn.Module):
     fused into the following LayerNorm (mc_add_layernorm), the way the Mamba
     blocks fuse add + RMSNorm.  Same math as x = x + attn(norm1(x));
     x = x + mlp(norm2(x)).
+
+    causal: causal self-attention (the CLIP text transformer).  act: "gelu", the exact GELU inside the
+    fused MLP (ops.mlp), or "quick_gelu", x * sigmoid(1.702 x) of the OpenAI CLIP weights, which runs
+    unfused: fc1 GEMM, torch elementwise, fc2 GEMM (ops.mlp's epilogue is exact-GELU only).
     """
 
-    def __init__(self, dim, heads, mlp_ratio=4.0):
+    def __init__(self, dim, heads, mlp_ratio=4.0, eps=1e-6, causal=False, act="gelu"):
         super().__init__()
-        self.norm1 = nn.LayerNorm(dim, eps=1e-6)
-        self.attn = Attention(dim, heads)
-        self.norm2 = nn.LayerNorm(dim, eps=1e-6)
+        if act not in ("gelu", "quick_gelu"):
+            raise ValueError(f"ViTBlock: act must be 'gelu' or 'quick_gelu', got {act!r}")
+        self.act = act
+        self.norm1 = nn.LayerNorm(dim, eps=eps)
+        self.attn = Attention(dim, heads, causal=causal)
+        self.norm2 = nn.LayerNorm(dim, eps=eps)
         self.fc1 = nn.Linear(dim, int(dim * mlp_ratio))
         self.fc2 = nn.Linear(int(dim * mlp_ratio), dim)
 
@@ -367,6 +384,9 @@ class ViTBlock(nn.Module):
         y, h = add_layernorm(m, h, self.norm1.weight, self.norm1.bias, self.norm1.eps)
         a = self.attn(y)
         y, h = add_layernorm(a, h, self.norm2.weight, self.norm2.bias, self.norm2.eps)
+        if self.act == "quick_gelu":
+            u = linear_sk(y, self.fc1.weight, self.fc1.bias)
+            return linear_sk(u * torch.sigmoid(1.702 * u), self.fc2.weight, self.fc2.bias), h
         return mlp(y, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias), h
 
 
@@ -382,22 +402,31 @@ class VisionTransformer(nn.Module):
     pools the class row, so the features do not depend on that order.  In eval() or with p == 0 the
     forward runs the ops it runs without the option.  The indices come from torch's generator of the
     input's device (ops.patch_keep_indices: torch.manual_seed governs them, no host sync);
-    `last_keep` holds those of the latest dropped forward, None after a full one."""
+    `last_keep` holds those of the latest dropped forward, None after a full one.
+
+    The defaults are the timm shape.  pre_norm=True, eps=1e-5, patch_bias=False (and act="quick_gelu"
+    for the OpenAI weights) give the CLIP vision tower of transformers / open_clip: `ln_pre` normalises
+    every token row right after the position add (per token, so patch dropout commutes with it);
+    load_hf_clip_state_dict fills it, tests/golden/clip_hf_tiny_vision*.safetensors pin it to
+    transformers.CLIPVisionModelWithProjection."""
 
     last_keep = None
 
-    def __init__(self, img_size=224, patch=16, width=768, layers=12, heads=12, output_dim=512, patch_dropout=0.0):
+    def __init__(self, img_size=224, patch=16, width=768, layers=12, heads=12, output_dim=512, patch_dropout=0.0,
+                 pre_norm=False, eps=1e-6, patch_bias=True, act="gelu"):
         super().__init__()
         if not 0.0 <= patch_dropout < 1.0:
             raise ValueError(f"VisionTransformer: patch_dropout must be in [0, 1), got {patch_dropout}")
         self.patch_dropout = float(patch_dropout)
         self.output_dim = output_dim
-        self.patch_embed = PatchEmbed(img_size, patch, 3, width)
+        self.patch_embed = PatchEmbed(img_size, patch, 3, width, bias=patch_bias)
         n = (img_size // patch) ** 2
         self.cls_token = nn.Parameter(torch.zeros(1, 1, width))
         self.pos_embed = nn.Parameter(torch.randn(1, n + 1, width) * 0.02)
-        self.blocks = nn.ModuleList([ViTBlock(width, heads) for _ in range(layers)])
-        self.norm = nn.LayerNorm(width, eps=1e-6)
+        if pre_norm:
+            self.ln_pre = nn.LayerNorm(width, eps=eps)
+        self.blocks = nn.ModuleList([ViTBlock(width, heads, eps=eps, act=act) for _ in range(layers)])
+        self.norm = nn.LayerNorm(width, eps=eps)
         self.head = nn.Linear(width, output_dim, bias=False)
         for m in self.modules():
             if isinstance(m, nn.Linear):
@@ -408,9 +437,8 @@ class VisionTransformer(nn.Module):
     def patch_dropout_active(self):
         return self.training and 0.0 < self.patch_dropout < 1.0
 
-    def forward(self, x, keep=None):
-        """keep ((B, n_keep) distinct patch indices per image) replaces the random draw; it is there for
-        tests and is honoured in training mode only."""
+    def _blocks_out(self, x, keep=None):
+        """(m, h) behind the last block: the hidden state is m + h."""
         if self.training and (keep is not None or self.patch_dropout_active()):
             # the selection sits in front of the blocks: gradient checkpointing recomputes blocks only
             n = self.pos_embed.shape[1] - 1
@@ -426,7 +454,20 @@ class VisionTransformer(nn.Module):
             x = self.patch_embed(x)
             # cat([cls, x]) + pos with a deterministic backward (ops.TokenEmbedFn)
             m, h = token_embed(self.cls_token, x, self.pos_embed), None
-        m, h = _run_blocks(self.blocks, m, h, self.grad_checkpointing and torch.is_grad_enabled())
+        if hasattr(self, "ln_pre"):
+            m = add_layernorm(m, None, self.ln_pre.weight, self.ln_pre.bias, self.ln_pre.eps)[0]
+        return _run_blocks(self.blocks, m, h, self.grad_checkpointing and torch.is_grad_enabled())
+
+    def forward_hidden(self, x, keep=None):
+        """The token rows behind the last block, before the final norm (B, tokens, width):
+        transformers' CLIPVisionModel last_hidden_state."""
+        m, h = self._blocks_out(x, keep)
+        return m + h
+
+    def forward(self, x, keep=None):
+        """keep ((B, n_keep) distinct patch indices per image) replaces the random draw; it is there for
+        tests and is honoured in training mode only."""
+        m, h = self._blocks_out(x, keep)
         # final norm on the pooled (cls) rows only: same values as norm(x)[:, 0]
         y, _ = add_layernorm(m[:, 0], h[:, 0], self.norm.weight, self.norm.bias, self.norm.eps)
         return self.head(y)
@@ -607,6 +648,176 @@ def load_hf_bert_state_dict(model, sd):
     return model
 
 
+# ============================================================================ CLIP text transformer
+class _PoolRowsFn(torch.autograd.Function):
+    """x[b, idx[b]] for x (B, N, C) and idx (B,) int64 on x's device.  Backward: zeros with row idx[b]
+    of batch b set to the gradient -- one row per batch, so the write is an index_copy with distinct
+    targets (deterministic; the scatter_add of gather's backward is not).  No host sync."""
+
+    @staticmethod
+    def forward(ctx, x, idx):
+        Bsz, N, C = x.shape
+        flat = torch.arange(Bsz, device=x.device) * N + idx
+        ctx.save_for_backward(flat)
+        ctx.shape = (Bsz, N, C)
+        return x.reshape(Bsz * N, C).index_select(0, flat)
+
+    @staticmethod
+    def backward(ctx, g):
+        (flat,) = ctx.saved_tensors
+        Bsz, N, C = ctx.shape
+        dx = g.new_zeros(Bsz * N, C)
+        dx.index_copy_(0, flat, g.contiguous())
+        return dx.view(Bsz, N, C), None
+
+
+class ClipTextEncoder(nn.Module):
+    """The CLIP text transformer (openai/clip-vit-base-patch16 and the open_clip ViT-B/16 checkpoints):
+    tokens (B, T <= context_length) int64 -> (B, output_dim).  Token + position embeddings (no embedding
+    LayerNorm) -> causal pre-LN blocks (ViTBlock(causal=True): the fused causal attention kernels under
+    bf16 / f16 autocast) -> the end-of-text row -> final LayerNorm -> bias-free text_projection.  The
+    final LayerNorm runs on the pooled rows only: the same values as ln_final(x)[arange, idx].
+
+    Pooling index: eot_token_id=None -> tokens.argmax(-1) (open_clip; the OpenAI tokenizer gives
+    end-of-text the largest id); an id -> the first position holding it (transformers, eos_token_id != 2).
+    The tower is causal, so whatever follows the end-of-text token never reaches the pooled row: no
+    padding mask.  act="quick_gelu" (the OpenAI weights; "gelu" for the LAION ones) runs the MLP
+    unfused (ViTBlock).  load_hf_clip_state_dict fills the tower; tests/golden/clip_hf_tiny_text*.safetensors
+    pin it to transformers.CLIPTextModelWithProjection."""
+
+    def __init__(self, vocab_size=49408, context_length=77, width=512, layers=12, heads=8, output_dim=512,
+                 eps=1e-5, act="quick_gelu", eot_token_id=None, mlp_dim=None):
+        super().__init__()
+        self.vocab_size, self.context_length, self.output_dim = vocab_size, context_length, output_dim
+        self.eot_token_id = None if eot_token_id is None else int(eot_token_id)
+        self.token_embedding = nn.Embedding(vocab_size, width)
+        self.positional_embedding = nn.Parameter(torch.empty(1, context_length, width))
+        self.blocks = nn.ModuleList([ViTBlock(width, heads, (mlp_dim or 4 * width) / width, eps=eps, causal=True, act=act)
+                                     for _ in range(layers)])
+        self.ln_final = nn.LayerNorm(width, eps=eps)
+        self.text_projection = nn.Linear(width, output_dim, bias=False)
+        # open_clip's CLIP text init
+        nn.init.normal_(self.token_embedding.weight, std=0.02)
+        nn.init.normal_(self.positional_embedding, std=0.01)
+        proj_std, attn_std, fc_std = (width ** -0.5) * ((2 * layers) ** -0.5), width ** -0.5, (2 * width) ** -0.5
+        for blk in self.blocks:
+            nn.init.normal_(blk.attn.qkv.weight, std=attn_std)
+            nn.init.normal_(blk.attn.proj.weight, std=proj_std)
+            nn.init.normal_(blk.fc1.weight, std=fc_std)
+            nn.init.normal_(blk.fc2.weight, std=proj_std)
+            for b in (blk.attn.qkv.bias, blk.attn.proj.bias, blk.fc1.bias, blk.fc2.bias):
+                nn.init.zeros_(b)
+        nn.init.normal_(self.text_projection.weight, std=width ** -0.5)
+
+    def lock_units(self):
+        """(embeddings, [block, ...], final norm) as lists of (name, parameter) for lock_text_tower."""
+        return ([("token_embedding.weight", self.token_embedding.weight),
+                 ("positional_embedding", self.positional_embedding)],
+                [list(b.named_parameters(prefix=f"blocks.{i}")) for i, b in enumerate(self.blocks)],
+                [("ln_final.weight", self.ln_final.weight), ("ln_final.bias", self.ln_final.bias)])
+
+    grad_checkpointing = False
+
+    def set_grad_checkpointing(self, enable=True):
+        """Activation checkpointing per transformer block (open_clip semantics)."""
+        self.grad_checkpointing = bool(enable)
+
+    def pool_index(self, tokens):
+        """(B,) int64 end-of-text positions, computed on the tokens' device (no host sync)."""
+        if self.eot_token_id is None:
+            return tokens.argmax(-1)
+        return (tokens == self.eot_token_id).int().argmax(-1)   # the first match (0 when there is none)
+
+    def _blocks_out(self, tokens):
+        T = tokens.shape[1]
+        if T > self.context_length:
+            raise ValueError(f"{T} tokens, the position table has {self.context_length}")
+        m, h = add_pos(self.token_embedding(tokens), self.positional_embedding), None
+        return _run_blocks(self.blocks, m, h, self.grad_checkpointing and torch.is_grad_enabled())
+
+    def forward_hidden(self, tokens):
+        """transformers' last_hidden_state: every row after the final LayerNorm, (B, T, width)."""
+        m, h = self._blocks_out(tokens)
+        return add_layernorm(m, h, self.ln_final.weight, self.ln_final.bias, self.ln_final.eps)[0]
+
+    def forward(self, tokens):
+        m, h = self._blocks_out(tokens)
+        idx = self.pool_index(tokens)
+        y, _ = add_layernorm(_PoolRowsFn.apply(m, idx), _PoolRowsFn.apply(h, idx), self.ln_final.weight,
+                             self.ln_final.bias, self.ln_final.eps)
+        return self.text_projection(y)
+
+
+_HF_CLIP_LAYER = {   # HF CLIPEncoderLayer name -> ViTBlock name (q_proj | k_proj | v_proj go into the packed qkv)
+    "self_attn.out_proj": "attn.proj", "layer_norm1": "norm1", "layer_norm2": "norm2", "mlp.fc1": "fc1", "mlp.fc2": "fc2",
+}
+
+
+def _hf_clip_blocks(blocks, pre, want, packed):
+    for i, blk in enumerate(blocks):
+        p = f"{pre}encoder.layers.{i}."
+        for hf, ours in _HF_CLIP_LAYER.items():
+            mod = blk.get_submodule(ours)
+            want[f"{p}{hf}.weight"], want[f"{p}{hf}.bias"] = (mod.weight, None), (mod.bias, None)
+        for wb in ("weight", "bias"):
+            packed[tuple(f"{p}self_attn.{n}.{wb}" for n in ("q_proj", "k_proj", "v_proj"))] = getattr(blk.attn.qkv, wb)
+
+
+def load_hf_clip_state_dict(clip_model, sd):
+    """Copy a transformers.CLIPModel state dict (text_model.*, vision_model.*, text_projection.weight,
+    visual_projection.weight, logit_scale) into a ClipModel of a pre_norm VisionTransformer and a
+    ClipTextEncoder.  q_proj | k_proj | v_proj pack into attn.qkv; class_embedding -> cls_token and
+    position_embedding.weight -> pos_embed / positional_embedding (reshaped to our (1, n, width));
+    pre_layrnorm (HF's spelling) -> ln_pre, post_layernorm -> norm, visual_projection -> head,
+    final_layer_norm -> ln_final.  Strict: a missing or an unexpected key raises KeyError, a shape
+    mismatch ValueError naming the tensor; only *.position_ids buffers are ignored."""
+    vis, txt = clip_model.visual, clip_model.text
+    if not (isinstance(vis, VisionTransformer) and hasattr(vis, "ln_pre") and isinstance(txt, ClipTextEncoder)):
+        raise TypeError("load_hf_clip_state_dict: needs a pre_norm VisionTransformer and a ClipTextEncoder")
+    sd = {k: v for k, v in sd.items() if not k.endswith(".position_ids")}
+    # HF name -> (parameter, shape the HF tensor is viewed as, or None for its own)
+    want = {"logit_scale": (clip_model.logit_scale, None),
+            "text_projection.weight": (txt.text_projection.weight, None),
+            "visual_projection.weight": (vis.head.weight, None),
+            "text_model.embeddings.token_embedding.weight": (txt.token_embedding.weight, None),
+            "text_model.embeddings.position_embedding.weight": (txt.positional_embedding, "lead1"),
+            "text_model.final_layer_norm.weight": (txt.ln_final.weight, None),
+            "text_model.final_layer_norm.bias": (txt.ln_final.bias, None),
+            "vision_model.embeddings.class_embedding": (vis.cls_token, "lead2"),
+            "vision_model.embeddings.patch_embedding.weight": (vis.patch_embed.proj.weight, None),
+            "vision_model.embeddings.position_embedding.weight": (vis.pos_embed, "lead1"),
+            "vision_model.pre_layrnorm.weight": (vis.ln_pre.weight, None),
+            "vision_model.pre_layrnorm.bias": (vis.ln_pre.bias, None),
+            "vision_model.post_layernorm.weight": (vis.norm.weight, None),
+            "vision_model.post_layernorm.bias": (vis.norm.bias, None)}
+    if vis.patch_embed.proj.bias is not None:
+        want["vision_model.embeddings.patch_embedding.bias"] = (vis.patch_embed.proj.bias, None)
+    packed = {}
+    _hf_clip_blocks(txt.blocks, "text_model.", want, packed)
+    _hf_clip_blocks(vis.blocks, "vision_model.", want, packed)
+    expected = set(want) | {n for names in packed for n in names}
+    missing, unexpected = sorted(expected - set(sd)), sorted(set(sd) - expected)
+    if missing or unexpected:
+        raise KeyError(f"load_hf_clip_state_dict: missing {missing}, unexpected {unexpected}")
+    copies = []
+    for name, (param, lead) in want.items():
+        t = sd[name]
+        shape = tuple(t.shape) if lead is None else (1,) * int(lead[4:]) + tuple(t.shape)
+        if shape != tuple(param.shape):
+            raise ValueError(f"load_hf_clip_state_dict: {name} is {tuple(t.shape)}, the model has {tuple(param.shape)}")
+        copies.append((param, t.reshape(shape)))
+    for names, param in packed.items():
+        parts = [sd[n] for n in names]
+        if any(t.shape != parts[0].shape for t in parts) or (3 * parts[0].shape[0],) + tuple(parts[0].shape[1:]) != tuple(param.shape):
+            raise ValueError(f"load_hf_clip_state_dict: {names[0]} (+ k_proj, v_proj) are {[tuple(t.shape) for t in parts]}, "
+                             f"the packed qkv has {tuple(param.shape)}")
+        copies.append((param, torch.cat(parts, 0)))
+    with torch.no_grad():
+        for param, t in copies:
+            param.copy_(t)
+    return clip_model
+
+
 # ============================================================================ CLIP wrapper (model.py:998-1112)
 def _is_norm_param(name):
     """Parameters of the modules the reference's lock_text_tower keeps under `freeze_layer_norm`:
@@ -650,7 +861,8 @@ class ClipModel(nn.Module):
     def side_priority(self):
         """HIP priority of the text-tower stream (-1 high, 0 normal, 1 low where the device has it):
         high beside the BERT tower (C3 25.3 -> 25.0 ms per step), normal beside the Mamba tower
-        (C2 69.9 -> 70.8 ms at high); profiles/r04/stream_priority/."""
+        (C2 69.9 -> 70.8 ms at high); profiles/r04/stream_priority/.  Beside the CLIP text transformer
+        it stays at the default, normal: unmeasured."""
         return -1 if isinstance(self.text, (BertTextEncoder, HFBertTextEncoder)) else 0
 
     def side_tower_module(self):
@@ -1071,6 +1283,10 @@ MODEL_CONFIGS = {
     # C3 with the text tower that computes transformers.BertModel (post-LN, token types, padding mask):
     # the one BiomedCLIP's PubMedBERT weights load into (load_hf_bert_state_dict)
     "biomedclip-vit_b16-pubmedbert256-hf": dict(vision=dict(), hf_bert=dict()),
+    # openai/clip-vit-base-patch16: the CLIP vision tower (pre-LN before the blocks, eps 1e-5, no patch bias,
+    # quick_gelu) with the CLIP text transformer (12 x 512, 8 heads, 77 tokens, causal, end-of-text pooling):
+    # the model a transformers.CLIPModel state dict loads into (load_hf_clip_state_dict)
+    "clip-vit_b16-hf": dict(vision=dict(pre_norm=True, eps=1e-5, patch_bias=False, act="quick_gelu"), clip_text=dict()),
 }
 
 
@@ -1080,7 +1296,9 @@ def build_clip(name, force_patch_dropout=None, **clip_kwargs):
     patch_dropout (the reference's --force-patch-dropout, cli/main.py:355-356)."""
     cfg = MODEL_CONFIGS[name]
     visual = VisionTransformer(**cfg["vision"], patch_dropout=force_patch_dropout or 0.0)
-    if "hf_bert" in cfg:
+    if "clip_text" in cfg:
+        text = ClipTextEncoder(**cfg["clip_text"])
+    elif "hf_bert" in cfg:
         text = HFBertTextEncoder(**cfg["hf_bert"])
     else:
         text = BertTextEncoder(**cfg["bert"]) if "bert" in cfg else MambaTextEncoder(**cfg["text"])

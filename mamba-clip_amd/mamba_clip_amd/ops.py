@@ -1828,9 +1828,10 @@ def attn_supported(seqlen, head_dim, dtype):
     return head_dim == 64 and 1 <= seqlen <= 256 and dtype in (torch.bfloat16, torch.float16)
 
 
-def _packed_attn_fwd(ctx, qkv, heads, words):
-    """Forward of PackedAttentionFn (words None: mc_attn_fwd) and PackedMaskedAttentionFn
-    (words (B, 8) int32 key bits: mc_attn_masked_fwd)."""
+def _packed_attn_fwd(ctx, qkv, heads, words, causal=False):
+    """Forward of PackedAttentionFn (words None: mc_attn_fwd), PackedMaskedAttentionFn
+    (words (B, 8) int32 key bits: mc_attn_masked_fwd) and PackedCausalAttentionFn (causal:
+    mc_attn_causal_fwd, the unmasked parameter struct)."""
     Bsz, N, C3 = qkv.shape
     C = C3 // 3
     D = C // heads
@@ -1849,7 +1850,10 @@ def _packed_attn_fwd(ctx, qkv, heads, words):
     p.q_bs, p.q_ns, p.q_hs = y.stride(0), y.stride(1), D
     p.o, p.o_bs, p.o_ns, p.o_hs = o.data_ptr(), o.stride(0), o.stride(1), D
     p.lse = lse.data_ptr()
-    if words is None:
+    if causal:
+        _lib.check(lib.mc_attn_causal_fwd(p, _lib.stream_handle(qkv.device)), "mc_attn_causal_fwd")
+        ctx.save_for_backward(y, o, lse)
+    elif words is None:
         _lib.check(lib.mc_attn_fwd(p, _lib.stream_handle(qkv.device)), "mc_attn_fwd")
         ctx.save_for_backward(y, o, lse)
     else:
@@ -1857,6 +1861,7 @@ def _packed_attn_fwd(ctx, qkv, heads, words):
         _lib.check(lib.mc_attn_masked_fwd(p, _lib.stream_handle(qkv.device)), "mc_attn_masked_fwd")
         ctx.save_for_backward(y, o, lse, words)
     ctx.heads = heads
+    ctx.causal = causal
     return o
 
 
@@ -1886,7 +1891,9 @@ def _packed_attn_bwd(ctx, go):
     # (LinearSK picks it up instead of a second pass over the (B*N, 3C) gradient)
     dsum = torch.empty(Bsz, 3 * C, device=y.device, dtype=torch.float32)
     p.dsum = dsum.data_ptr()
-    if words is None:
+    if ctx.causal:
+        _lib.check(lib.mc_attn_causal_bwd(p, _lib.stream_handle(y.device)), "mc_attn_causal_bwd")
+    elif words is None:
         _lib.check(lib.mc_attn_bwd(p, _lib.stream_handle(y.device)), "mc_attn_bwd")
     else:   # dk / dv of masked keys come back as stored zeros (dy is empty_like)
         p.key_mask = words.data_ptr()
@@ -1931,8 +1938,26 @@ class PackedMaskedAttentionFn(torch.autograd.Function):
         return _packed_attn_bwd(ctx, go), None, None
 
 
-def packed_attention(qkv, heads, key_mask=None):
-    """key_mask None: unmasked (PackedAttentionFn); else pack_key_mask(valid) words."""
+class PackedCausalAttentionFn(torch.autograd.Function):
+    """PackedAttentionFn with the causal mask (query i attends to keys j <= i: the CLIP text
+    transformer).  mc_attn_causal_fwd / _bwd: key tiles above the diagonal are never visited."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads):
+        return _packed_attn_fwd(ctx, qkv, heads, None, causal=True)
+
+    @staticmethod
+    def backward(ctx, go):
+        return _packed_attn_bwd(ctx, go), None
+
+
+def packed_attention(qkv, heads, key_mask=None, causal=False):
+    """key_mask None: unmasked (PackedAttentionFn), or with causal=True PackedCausalAttentionFn;
+    else pack_key_mask(valid) words.  The causal and the key-padding mask do not combine."""
+    if causal:
+        if key_mask is not None:
+            raise ValueError("packed_attention: causal=True with a key_mask is not supported")
+        return PackedCausalAttentionFn.apply(qkv, heads)
     if key_mask is None:
         return PackedAttentionFn.apply(qkv, heads)
     return PackedMaskedAttentionFn.apply(qkv, heads, key_mask)

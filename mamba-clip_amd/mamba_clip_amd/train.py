@@ -80,7 +80,9 @@ def get_model_inputs(args, images, texts, targets=None, balanced_images=None, ba
 
 # ---------------------------------------------------------------- optimizer / DDP (pipeline.py:266-311)
 def _no_decay(name, p):
-    return p.ndim < 2 or "bn" in name or "ln" in name or "bias" in name or "logit_scale" in name
+    # positional_embedding: the CLIP text transformer's learned position table (ClipTextEncoder)
+    return (p.ndim < 2 or "bn" in name or "ln" in name or "bias" in name or "logit_scale" in name
+            or "positional_embedding" in name)
 
 
 def create_optimizer(model, args):
