@@ -185,7 +185,10 @@ int32_t mc_scan_n_states(int32_t seqlen, int32_t state_interval);
 /* the interval mc_scan_fwd will save states with for these params: p->state_interval when
  * the call can honour it (MC_SCAN_STATE_INTERVAL_FINE needs the pair kernel's shapes),
  * else MC_SCAN_CHUNK.  Size chunk_states with mc_scan_n_states(seqlen, result) and pass
- * the result to both mc_scan_fwd and mc_scan_bwd. */
+ * the result to both mc_scan_fwd and mc_scan_bwd.  Answered from the choice mc_scan_fwd itself
+ * runs on, which reads shapes, strides and pointer alignment only: it answers for any params,
+ * an empty call included, reports no error and leaves mc_last_error() alone.  n_groups == 0
+ * (no channels per group to divide into) gives MC_SCAN_CHUNK. */
 int32_t mc_scan_fwd_state_interval(const mc_scan_fwd_params* p);
 
 /* workspace the forward needs (B/C re-laid out as fp32 [batch][group][seqlen][2*dstate']) */
@@ -198,7 +201,10 @@ size_t mc_scan_bwd_workspace_bytes(int32_t batch, int32_t dim, int32_t seqlen, i
 /* Which kernel family mc_scan_fwd / mc_scan_bwd run for these params (no launch; for tests and
  * tooling): the lane-pair kernels (16-bit rows, dstate 16, seqlen % 8 == 0, 16-B aligned rows:
  * scan_fwd_pair.hip / scan_bwd_pair.hip), the general chunked kernels, or the grouped-direction
- * (SS2D) path.  NONE for an empty call. */
+ * (SS2D) path.  NONE for an empty call.  The answer is the choice the call itself executes; it depends on
+ * shapes, strides and pointer alignment only, so it is given for any params, also ones the call would
+ * reject; the queries report no error and leave mc_last_error() alone.  mc_scan_fwd_kernel with
+ * n_groups == 0 (no channels per group to divide into) gives MC_SCAN_KERNEL_NONE. */
 #define MC_SCAN_KERNEL_NONE 0
 #define MC_SCAN_KERNEL_PAIR 1
 #define MC_SCAN_KERNEL_GENERIC 2

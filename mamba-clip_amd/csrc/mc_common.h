@@ -304,6 +304,20 @@ inline int check_launch(const char* who) {
   return MC_OK;
 }
 
+// a runtime flag as the compile-time constant `name`
+#define MC_DISPATCH_BOOL(flag, name, ...)                 \
+  do {                                                    \
+    if (flag) { constexpr bool name = true; __VA_ARGS__; } \
+    else { constexpr bool name = false; __VA_ARGS__; }     \
+  } while (0)
+
+#define MC_DISPATCH_T(dtype, ...)                                   \
+  do {                                                              \
+    if ((dtype) == MC_DTYPE_F32) { using T = float; __VA_ARGS__; }  \
+    else if ((dtype) == MC_DTYPE_BF16) { using T = bf16_t; __VA_ARGS__; } \
+    else { using T = f16_t; __VA_ARGS__; }                          \
+  } while (0)
+
 // Bijective blockIdx remap so that consecutive logical blocks (neighbours that
 // share operands) run on one XCD: hardware deals blocks round-robin over
 // the 8 XCDs (speed only -- correctness never depends on placement).

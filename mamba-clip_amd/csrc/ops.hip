@@ -1158,20 +1158,6 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(int rows, int cols, con
 using namespace mc;
 using namespace mc::ops;
 
-// a runtime flag as the compile-time constant `name`
-#define MC_DISPATCH_BOOL(flag, name, ...)                 \
-  do {                                                    \
-    if (flag) { constexpr bool name = true; __VA_ARGS__; } \
-    else { constexpr bool name = false; __VA_ARGS__; }     \
-  } while (0)
-
-#define MC_DISPATCH_T(dtype, ...)                                   \
-  do {                                                              \
-    if ((dtype) == MC_DTYPE_F32) { using T = float; __VA_ARGS__; }  \
-    else if ((dtype) == MC_DTYPE_BF16) { using T = bf16_t; __VA_ARGS__; } \
-    else { using T = f16_t; __VA_ARGS__; }                          \
-  } while (0)
-
 // The entry checks every norm shares: the dtype, then V = elements per 16-B vector and cols a whole number of
 // vectors that one wave holds in registers (rows: 0 where the entry point counts no rows).
 static int norm_check(const char* who, int dtype, int rows, int cols, int* V) {

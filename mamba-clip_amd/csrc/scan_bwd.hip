@@ -626,20 +626,14 @@ __global__ __launch_bounds__(256) void bc_quad_kernel(const TW* __restrict__ B, 
   }
 }
 
-template <typename TW>
-static hipError_t launch_bc_quads(const mc_scan_bwd_params* p, int np, f32x4* out, hipStream_t s) {
+static hipError_t launch_bc_quads(const mc_scan_bwd_params* p, f32x4* out, hipStream_t s) {
+  const int np = padded_dstate(p->dstate);
   const int64_t total = (int64_t)p->batch * p->n_groups * p->seqlen * (np / 2);
   const int grid = (int)std::min<int64_t>((total + 255) / 256, 8192);
-  const TW* B = reinterpret_cast<const TW*>(p->B);
-  const TW* C = reinterpret_cast<const TW*>(p->C);
-#define MC_BCQ(NP)                                                                                                 \
-  hipLaunchKernelGGL((bc_quad_kernel<TW, NP>), grid, 256, 0, s, B, C, p->B_batch_stride, p->B_group_stride,       \
-                     p->B_dstate_stride, p->C_batch_stride, p->C_group_stride, p->C_dstate_stride, p->batch,      \
-                     p->n_groups, p->seqlen, p->dstate, p->reverse_groups, out)
-  if (np == 8) MC_BCQ(8);
-  else if (np == 16) MC_BCQ(16);
-  else MC_BCQ(32);
-#undef MC_BCQ
+  MC_DISPATCH_T(p->wtype, MC_DISPATCH_NP(np, hipLaunchKernelGGL(
+      (bc_quad_kernel<T, kN>), grid, 256, 0, s, reinterpret_cast<const T*>(p->B), reinterpret_cast<const T*>(p->C),
+      p->B_batch_stride, p->B_group_stride, p->B_dstate_stride, p->C_batch_stride, p->C_group_stride,
+      p->C_dstate_stride, p->batch, p->n_groups, p->seqlen, p->dstate, p->reverse_groups, out)));
   return hipGetLastError();
 }
 
@@ -750,92 +744,130 @@ static size_t bwd_lds_bytes() {
          (size_t)2 * kRows * 3 * (kTB / 2) * 4 + (size_t)kTB * 2 * kN * 4;
 }
 
-template <typename TI, int kN>
-static int launch_bwd_n(const BwdArgs& a, bool aligned, hipStream_t s) {
-  const size_t lds = bwd_lds_bytes<TI, kN>();
-  if (a.rev_groups || a.u_groups) {   // grouped directions (SS2D)
-    if (aligned && a.softplus)
-      hipLaunchKernelGGL((scan_bwd_kernel<TI, kN, true, true, true>), dim3(a.total_blocks), dim3(kWG), lds, s, a);
-    else if (aligned)
-      hipLaunchKernelGGL((scan_bwd_kernel<TI, kN, true, false, true>), dim3(a.total_blocks), dim3(kWG), lds, s, a);
-    else if (a.softplus)
-      hipLaunchKernelGGL((scan_bwd_kernel<TI, kN, false, true, true>), dim3(a.total_blocks), dim3(kWG), lds, s, a);
-    else
-      hipLaunchKernelGGL((scan_bwd_kernel<TI, kN, false, false, true>), dim3(a.total_blocks), dim3(kWG), lds, s,
-                         a);
-  } else if (aligned && a.softplus)
-    hipLaunchKernelGGL((scan_bwd_kernel<TI, kN, true, true>), dim3(a.total_blocks), dim3(kWG), lds, s, a);
-  else if (aligned)
-    hipLaunchKernelGGL((scan_bwd_kernel<TI, kN, true, false>), dim3(a.total_blocks), dim3(kWG), lds, s, a);
-  else if (a.softplus)
-    hipLaunchKernelGGL((scan_bwd_kernel<TI, kN, false, true>), dim3(a.total_blocks), dim3(kWG), lds, s, a);
-  else
-    hipLaunchKernelGGL((scan_bwd_kernel<TI, kN, false, false>), dim3(a.total_blocks), dim3(kWG), lds, s, a);
-  const hipError_t e = hipGetLastError();
-  MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "mc_scan_bwd: launch failed: %s", hipGetErrorString(e));
+// scan_bwd_pair.hip: the lane-pair kernel for 16-bit rows with dstate 16 (the text towers); it reads 16-bit
+// B / C rows directly (no quad relayout)
+void launch_bwd_pair(const mc_scan_bwd_params* p, const BwdSlabs& w, hipStream_t s);
+
+// Everything mc_scan_bwd does for a call, decided in one place; mc_scan_bwd_kernel reads the same plan.
+struct BwdPlan {
+  int family = MC_SCAN_KERNEL_NONE;   // MC_SCAN_KERNEL_*; NONE: nothing to launch
+  bool aligned = false;               // general kernel: 16-B vector rows
+  f32x4* bq = nullptr;                // workspace: the general kernel's B / C quads
+  int rows = kRows;                   // channels per workgroup of the chosen kernel
+  BwdSlabs slabs{};                   // workspace: partial sums, one dB / dC slab per `rows` channels
+  BwdArgs a{};                        // general kernel
+};
+
+// The choice: what a call with these params runs.  It reads shapes, strides and pointer alignment only,
+// reports no error and touches nothing else, so mc_scan_bwd_kernel answers from it for any params.
+static void choose_bwd(const mc_scan_bwd_params* p, BwdPlan& pl) {
+  pl = BwdPlan{};
+  const bool empty = p->batch == 0 || p->seqlen == 0, dirs = has_dirs(p->reverse_groups, p->u_groups);
+  const int ib = elem_bytes(p->itype);
+  const Rows rows[] = {{p->u, p->u_batch_stride, p->u_dim_stride},
+                       {p->delta, p->delta_batch_stride, p->delta_dim_stride},
+                       {p->z, p->z_batch_stride, p->z_dim_stride},
+                       {p->dout, p->dout_batch_stride, p->dout_dim_stride},
+                       {p->du, p->du_batch_stride, p->du_dim_stride},
+                       {p->ddelta, p->ddelta_batch_stride, p->ddelta_dim_stride},
+                       {p->dz, p->dz_batch_stride, p->dz_dim_stride}};
+  const bool vec = all_vec_ok(rows, ib);
+  // the pair kernel also addresses its workgroup's saved states with 32-bit byte offsets
+  const bool pair = pair_shape_ok(p, kQN) && vec && all_span32(rows, kQCh * kQW, p->seqlen, ib) &&
+                    (int64_t)kQCh * kQW * mc_scan_n_states(p->seqlen, p->state_interval) * kQN * 4 < ((int64_t)1 << 31);
+  pl.family = empty ? MC_SCAN_KERNEL_NONE
+                    : dirs ? MC_SCAN_KERNEL_DIRS : pair ? MC_SCAN_KERNEL_PAIR : MC_SCAN_KERNEL_GENERIC;
+  pl.rows = pair ? kQCh * kQW : kRows;
+  // the vector path addresses a workgroup's 64 rows with 32-bit byte offsets; mirrored blocks stay aligned
+  pl.aligned = !pair && vec && all_span32(rows, kRows, (int64_t)p->seqlen + kTC, ib) && dirs_vec_ok(dirs, p->seqlen, ib);
+}
+
+// The checks of a call, in the ABI's order, around the choice; then the workspace carving and the args.
+static int plan_bwd(const mc_scan_bwd_params* p, BwdPlan& pl) {
+  MC_CHECK(p != nullptr, MC_ERR_INVALID, "mc_scan_bwd: null params");
+  choose_bwd(p, pl);
+  MC_TRY(validate_common(p->batch, p->dim, p->seqlen, p->dstate, p->n_groups, p->itype, p->wtype, "mc_scan_bwd"));
+  const bool dirs = pl.family == MC_SCAN_KERNEL_DIRS;
+  const int np = padded_dstate(p->dstate);
+  MC_CHECK(p->A && p->dA, MC_ERR_INVALID, "mc_scan_bwd: A and dA must be non-null");
+  MC_CHECK(!p->D || p->dD, MC_ERR_INVALID, "mc_scan_bwd: dD required when D is given");
+  MC_CHECK(!p->delta_bias || p->ddelta_bias, MC_ERR_INVALID, "mc_scan_bwd: ddelta_bias required with delta_bias");
+  if (pl.family == MC_SCAN_KERNEL_NONE) return MC_OK;
+  MC_CHECK(p->u && p->delta && p->B && p->C && p->dout && p->du && p->ddelta && p->dB && p->dC, MC_ERR_INVALID,
+           "mc_scan_bwd: u, delta, B, C, dout and du, ddelta, dB, dC must be non-null");
+  MC_CHECK(!p->z || p->dz, MC_ERR_INVALID, "mc_scan_bwd: dz required when z is given");
+  MC_CHECK((int64_t)kRows * mc_scan_n_chunks(p->seqlen) * p->dstate * 4 < ((int64_t)1 << 31) &&
+               (int64_t)p->seqlen * (np / 2) * 16 < ((int64_t)1 << 31) &&
+               (int64_t)p->seqlen * 2 * np * 4 < ((int64_t)1 << 31),
+           MC_ERR_INVALID, "mc_scan_bwd: seqlen %d too long for 32-bit offsets", p->seqlen);
+  MC_CHECK(p->chunk_states, MC_ERR_INVALID, "mc_scan_bwd: chunk_states (from the training forward) required");
+  const int S = p->state_interval > 0 ? p->state_interval : kS;
+  MC_CHECK(S == kS || (S == kFineS && p->seqlen % kFineS == 0), MC_ERR_SHAPE,
+           "mc_scan_bwd: state_interval %d: 0 / %d, or %d with seqlen %% %d == 0 (the forward's interval)",
+           p->state_interval, kS, kFineS, kFineS);
+  // a workgroup's saved states, either kernel's
+  MC_CHECK((int64_t)kRows * mc_scan_n_states(p->seqlen, S) * p->dstate * 4 < ((int64_t)1 << 31) &&
+               (int64_t)kQCh * kQW * mc_scan_n_states(p->seqlen, S) * kQN * 4 < ((int64_t)1 << 31),
+           MC_ERR_INVALID, "mc_scan_bwd: seqlen %d too long for 32-bit state offsets", p->seqlen);
+  MC_TRY(check_dirs(p, "mc_scan_bwd"));
+  const BwdWs w = bwd_ws_layout(p->batch, p->dim, p->seqlen, p->dstate, p->n_groups);
+  MC_CHECK(p->workspace && p->workspace_bytes >= w.total && (reinterpret_cast<uintptr_t>(p->workspace) & 255) == 0,
+           MC_ERR_WORKSPACE, "mc_scan_bwd: workspace must be >= %zu bytes and 256-B aligned (got %zu)", w.total,
+           p->workspace_bytes);
+
+  char* ws = reinterpret_cast<char*>(p->workspace);
+  pl.bq = reinterpret_cast<f32x4*>(ws + w.bq);
+  pl.slabs = BwdSlabs{reinterpret_cast<float*>(ws + w.slab_bc), reinterpret_cast<float*>(ws + w.slab_a),
+                      reinterpret_cast<float*>(ws + w.slab_d), reinterpret_cast<float*>(ws + w.slab_bias)};
+  if (pl.family == MC_SCAN_KERNEL_PAIR) return MC_OK;   // scan_bwd_pair.hip fills its own args
+  fill_bwd_args(pl.a, p, pl.slabs, pl.rows);
+  pl.a.dstate = p->dstate;
+  pl.a.softplus = p->delta_softplus;
+  pl.a.bq = reinterpret_cast<const float*>(pl.bq);
+  pl.a.rev_groups = dirs ? p->reverse_groups : 0; pl.a.u_groups = dirs ? p->u_groups : 0;
   return MC_OK;
 }
 
-template <typename TI>
-static int launch_bwd_t(const BwdArgs& a, bool aligned, hipStream_t s) {
-  const int np = padded_dstate(a.dstate);
-  if (np == 8) return launch_bwd_n<TI, 8>(a, aligned, s);
-  if (np == 16) return launch_bwd_n<TI, 16>(a, aligned, s);
-  return launch_bwd_n<TI, 32>(a, aligned, s);
+static int launch_bwd_generic(const BwdPlan& pl, int itype, hipStream_t s) {
+  const BwdArgs& a = pl.a;
+  const dim3 grid(a.total_blocks), block(kWG);
+  MC_DISPATCH_T(itype, MC_DISPATCH_NP(padded_dstate(a.dstate), MC_DISPATCH_BOOL(pl.aligned, kAl, MC_DISPATCH_BOOL(
+      a.softplus != 0, kSP, MC_DISPATCH_BOOL(a.rev_groups || a.u_groups, kDirs, hipLaunchKernelGGL(
+          (scan_bwd_kernel<T, kN, kAl, kSP, kDirs>), grid, block, (bwd_lds_bytes<T, kN>()), s, a))))));
+  return check_launch("mc_scan_bwd");
 }
 
-template <typename TW, int kN>
-static void launch_reduce(const BwdArgs& a, void* dB, void* dC, float* dA, float* dD, float* dbias, hipStream_t s) {
-  const int64_t total = (int64_t)a.batch * a.n_groups * kN * 2 * a.seqlen;
+// dB / dC: sum the slabs of the workgroups (`rows` channels each) into the outputs, whose strides come from
+// the params (all zero: contiguous (batch, G, dstate, seqlen)); dA / dD / dbias: sum the per-batch slabs.
+static int launch_reduce(const mc_scan_bwd_params* p, const BwdSlabs& w, int rows, hipStream_t s) {
+  const int np = padded_dstate(p->dstate), nblk = (p->dim / p->n_groups + rows - 1) / rows;
+  BcOutStrides os = {{{p->dB_batch_stride, p->dB_group_stride, p->dB_dstate_stride},
+                      {p->dC_batch_stride, p->dC_group_stride, p->dC_dstate_stride}}};
+  for (auto& st : os.s)
+    if (st[0] == 0 && st[1] == 0 && st[2] == 0) {
+      st[0] = (int64_t)p->n_groups * p->dstate * p->seqlen; st[1] = (int64_t)p->dstate * p->seqlen; st[2] = p->seqlen;
+    }
+  const int64_t total = (int64_t)p->batch * p->n_groups * np * 2 * p->seqlen;
   const int grid = (int)std::min<int64_t>((total + 255) / 256, 16384);
-  hipLaunchKernelGGL((scan_bwd_reduce_bc<TW, kN>), dim3(grid), dim3(256), 0, s, a.slab_bc, a.batch, a.n_groups,
-                     a.nblk, a.dstate, a.seqlen, a.rev_groups, reinterpret_cast<TW*>(dB),
-                     reinterpret_cast<TW*>(dC), BcOutStrides{{{a.bc_out_s[0][0], a.bc_out_s[0][1], a.bc_out_s[0][2]},
-                                                             {a.bc_out_s[1][0], a.bc_out_s[1][1], a.bc_out_s[1][2]}}});
+  MC_DISPATCH_T(p->wtype, MC_DISPATCH_NP(np, hipLaunchKernelGGL(
+      (scan_bwd_reduce_bc<T, kN>), dim3(grid), dim3(256), 0, s, w.bc, p->batch, p->n_groups, nblk, p->dstate,
+      p->seqlen, p->reverse_groups, reinterpret_cast<T*>(p->dB), reinterpret_cast<T*>(p->dC), os)));
   // slab_a is [b][n][d]: column c = n * dim + d -> dA[d][n] (transposed on output)
-  const int ca = a.dim * a.dstate;
-  hipLaunchKernelGGL(scan_bwd_colsum_nd, dim3((ca + 31) / 32), dim3(256), 0, s, a.slab_a, a.batch, a.dim, a.dstate,
-                     (int64_t)a.dim * kN, dA);
+  const int ca = p->dim * p->dstate;
+  hipLaunchKernelGGL(scan_bwd_colsum_nd, dim3((ca + 31) / 32), dim3(256), 0, s, w.a, p->batch, p->dim, p->dstate,
+                     (int64_t)p->dim * np, p->dA);
+  float* dD = p->dD; float* dbias = p->ddelta_bias;
   if (dD && dbias)
-    hipLaunchKernelGGL(scan_bwd_colsum, dim3((a.dim + 31) / 32, 2), dim3(256), 0, s, a.slab_d, a.slab_bias, a.batch,
-                       a.dim, (int64_t)a.dim, dD, dbias);
+    hipLaunchKernelGGL(scan_bwd_colsum, dim3((p->dim + 31) / 32, 2), dim3(256), 0, s, w.d, w.bias, p->batch, p->dim,
+                       (int64_t)p->dim, dD, dbias);
   else if (dD || dbias)
-    hipLaunchKernelGGL(scan_bwd_colsum, dim3((a.dim + 31) / 32), dim3(256), 0, s, dD ? a.slab_d : a.slab_bias,
-                       nullptr, a.batch, a.dim, (int64_t)a.dim, dD ? dD : dbias, nullptr);
+    hipLaunchKernelGGL(scan_bwd_colsum, dim3((p->dim + 31) / 32), dim3(256), 0, s, dD ? w.d : w.bias, nullptr,
+                       p->batch, p->dim, (int64_t)p->dim, dD ? dD : dbias, nullptr);
+  const hipError_t e = hipGetLastError();
+  MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "mc_scan_bwd: reduce launch failed: %s", hipGetErrorString(e));
+  return MC_OK;
 }
 
-// dB / dC output strides from the params (all zero: contiguous (batch, G, dstate, seqlen))
-static void set_bc_out_strides(BwdArgs& a, const mc_scan_bwd_params* p) {
-  const int64_t ps[2][3] = {{p->dB_batch_stride, p->dB_group_stride, p->dB_dstate_stride},
-                            {p->dC_batch_stride, p->dC_group_stride, p->dC_dstate_stride}};
-  for (int w = 0; w < 2; ++w) {
-    const bool dflt = ps[w][0] == 0 && ps[w][1] == 0 && ps[w][2] == 0;
-    a.bc_out_s[w][0] = dflt ? (int64_t)a.n_groups * a.dstate * a.seqlen : ps[w][0];
-    a.bc_out_s[w][1] = dflt ? (int64_t)a.dstate * a.seqlen : ps[w][1];
-    a.bc_out_s[w][2] = dflt ? (int64_t)a.seqlen : ps[w][2];
-  }
-}
-
-template <typename TW>
-static void launch_reduce_t(BwdArgs& a, const mc_scan_bwd_params* p, void* dB, void* dC, float* dA, float* dD,
-                            float* dbias, hipStream_t s) {
-  set_bc_out_strides(a, p);
-  const int np = padded_dstate(a.dstate);
-  if (np == 8) launch_reduce<TW, 8>(a, dB, dC, dA, dD, dbias, s);
-  else if (np == 16) launch_reduce<TW, 16>(a, dB, dC, dA, dD, dbias, s);
-  else launch_reduce<TW, 32>(a, dB, dC, dA, dD, dbias, s);
-}
-
-}  // namespace scan
-}  // namespace mc
-
-namespace mc {
-namespace scan {
-// scan_bwd_pair.hip: the lane-pair kernel for 16-bit rows with dstate 16 (the text towers)
-bool bwd_pair_ok(const mc_scan_bwd_params* p);
-int bwd_pair_nblk(int H);
-void launch_bwd_pair(const mc_scan_bwd_params* p, float* slab_bc, float* slab_a, float* slab_d, float* slab_bias,
-                     int nblk, hipStream_t s);
 }  // namespace scan
 }  // namespace mc
 
@@ -849,131 +881,29 @@ extern "C" size_t mc_scan_bwd_workspace_bytes(int32_t batch, int32_t dim, int32_
 }
 
 extern "C" int32_t mc_scan_bwd_kernel(const mc_scan_bwd_params* p) {
-  if (!p || p->batch == 0 || p->seqlen == 0) return MC_SCAN_KERNEL_NONE;
-  if (p->reverse_groups != 0 || p->u_groups != 0) return MC_SCAN_KERNEL_DIRS;
-  return bwd_pair_ok(p) ? MC_SCAN_KERNEL_PAIR : MC_SCAN_KERNEL_GENERIC;
+  BwdPlan pl;
+  if (p) choose_bwd(p, pl);
+  return pl.family;
 }
 
 extern "C" int mc_scan_bwd(const mc_scan_bwd_params* p, void* stream) {
-  MC_CHECK(p != nullptr, MC_ERR_INVALID, "mc_scan_bwd: null params");
-  int rc = validate_common(p->batch, p->dim, p->seqlen, p->dstate, p->n_groups, p->itype, p->wtype, "mc_scan_bwd");
-  if (rc) return rc;
-  MC_CHECK(p->A && p->dA, MC_ERR_INVALID, "mc_scan_bwd: A and dA must be non-null");
-  MC_CHECK(!p->D || p->dD, MC_ERR_INVALID, "mc_scan_bwd: dD required when D is given");
-  MC_CHECK(!p->delta_bias || p->ddelta_bias, MC_ERR_INVALID, "mc_scan_bwd: ddelta_bias required with delta_bias");
+  BwdPlan pl;
+  MC_TRY(plan_bwd(p, pl));
   hipStream_t s = (hipStream_t)stream;
-  const int np = padded_dstate(p->dstate);
-  if (p->batch == 0 || p->seqlen == 0) {
+  if (pl.family == MC_SCAN_KERNEL_NONE) {
     // no positions: parameter gradients are zero, per-position gradients are empty
     (void)hipMemsetAsync(p->dA, 0, (size_t)p->dim * p->dstate * 4, s);
     if (p->dD) (void)hipMemsetAsync(p->dD, 0, (size_t)p->dim * 4, s);
     if (p->ddelta_bias) (void)hipMemsetAsync(p->ddelta_bias, 0, (size_t)p->dim * 4, s);
     return MC_OK;
   }
-  MC_CHECK(p->u && p->delta && p->B && p->C && p->dout && p->du && p->ddelta && p->dB && p->dC, MC_ERR_INVALID,
-           "mc_scan_bwd: u, delta, B, C, dout and du, ddelta, dB, dC must be non-null");
-  MC_CHECK(!p->z || p->dz, MC_ERR_INVALID, "mc_scan_bwd: dz required when z is given");
-  MC_CHECK((int64_t)kRows * mc_scan_n_chunks(p->seqlen) * p->dstate * 4 < ((int64_t)1 << 31) &&
-               (int64_t)p->seqlen * (np / 2) * 16 < ((int64_t)1 << 31) &&
-               (int64_t)p->seqlen * 2 * np * 4 < ((int64_t)1 << 31),
-           MC_ERR_INVALID, "mc_scan_bwd: seqlen %d too long for 32-bit offsets", p->seqlen);
-  MC_CHECK(p->chunk_states, MC_ERR_INVALID, "mc_scan_bwd: chunk_states (from the training forward) required");
-  const int S = p->state_interval > 0 ? p->state_interval : kS;
-  MC_CHECK(S == kS || (S == kFineS && p->seqlen % kFineS == 0), MC_ERR_SHAPE,
-           "mc_scan_bwd: state_interval %d: 0 / %d, or %d with seqlen %% %d == 0 (the forward's interval)",
-           p->state_interval, kS, kFineS, kFineS);
-  MC_CHECK((int64_t)kRows * mc_scan_n_states(p->seqlen, S) * p->dstate * 4 < ((int64_t)1 << 31) &&
-               (int64_t)128 * mc_scan_n_states(p->seqlen, S) * 16 * 4 < ((int64_t)1 << 31),   // pair kernel: 128 rows
-           MC_ERR_INVALID, "mc_scan_bwd: seqlen %d too long for 32-bit state offsets", p->seqlen);
-  const bool dirs = p->reverse_groups != 0 || p->u_groups != 0;
-  if (dirs) {
-    MC_CHECK(!p->z && p->u_groups >= 0 && p->u_groups <= p->n_groups && p->n_groups <= 31 &&
-                 (p->reverse_groups >> p->n_groups) == 0,
-             MC_ERR_SHAPE, "mc_scan_bwd: reverse_groups / u_groups need no z, 0 <= u_groups <= n_groups <= 31 and "
-             "a mask within n_groups (got mask 0x%x, u_groups %d, n_groups %d)", p->reverse_groups, p->u_groups,
-             p->n_groups);
+  if (pl.family == MC_SCAN_KERNEL_PAIR) {
+    launch_bwd_pair(p, pl.slabs, s);
+    MC_TRY(check_launch("mc_scan_bwd"));
+  } else {
+    const hipError_t e = launch_bc_quads(p, pl.bq, s);
+    MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "mc_scan_bwd: B/C quad relayout launch failed: %s", hipGetErrorString(e));
+    MC_TRY(launch_bwd_generic(pl, p->itype, s));
   }
-  const BwdWs w = bwd_ws_layout(p->batch, p->dim, p->seqlen, p->dstate, p->n_groups);
-  MC_CHECK(p->workspace && p->workspace_bytes >= w.total && (reinterpret_cast<uintptr_t>(p->workspace) & 255) == 0,
-           MC_ERR_WORKSPACE, "mc_scan_bwd: workspace must be >= %zu bytes and 256-B aligned (got %zu)", w.total,
-           p->workspace_bytes);
-  char* ws = reinterpret_cast<char*>(p->workspace);
-  hipError_t e;
-  if (!dirs && bwd_pair_ok(p)) {
-    // lane-pair kernel: reads 16-bit B / C rows directly (no quad relayout); one slab per 128 channels
-    BwdArgs a{};
-    a.batch = p->batch; a.dim = p->dim; a.seqlen = p->seqlen; a.dstate = p->dstate; a.n_groups = p->n_groups;
-    a.nblk = bwd_pair_nblk(p->dim / p->n_groups);
-    a.slab_bc = reinterpret_cast<float*>(ws + w.slab_bc);
-    a.slab_a = reinterpret_cast<float*>(ws + w.slab_a);
-    a.slab_d = reinterpret_cast<float*>(ws + w.slab_d);
-    a.slab_bias = reinterpret_cast<float*>(ws + w.slab_bias);
-    launch_bwd_pair(p, a.slab_bc, a.slab_a, a.slab_d, a.slab_bias, a.nblk, s);
-    e = hipGetLastError();
-    MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "mc_scan_bwd: launch failed: %s", hipGetErrorString(e));
-    if (p->wtype == MC_DTYPE_F32) launch_reduce_t<float>(a, p, p->dB, p->dC, p->dA, p->dD, p->ddelta_bias, s);
-    else if (p->wtype == MC_DTYPE_BF16) launch_reduce_t<bf16_t>(a, p, p->dB, p->dC, p->dA, p->dD, p->ddelta_bias, s);
-    else launch_reduce_t<f16_t>(a, p, p->dB, p->dC, p->dA, p->dD, p->ddelta_bias, s);
-    e = hipGetLastError();
-    MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "mc_scan_bwd: reduce launch failed: %s", hipGetErrorString(e));
-    return MC_OK;
-  }
-  f32x4* bq = reinterpret_cast<f32x4*>(ws + w.bq);
-  if (p->wtype == MC_DTYPE_F32) e = launch_bc_quads<float>(p, np, bq, s);
-  else if (p->wtype == MC_DTYPE_BF16) e = launch_bc_quads<bf16_t>(p, np, bq, s);
-  else e = launch_bc_quads<f16_t>(p, np, bq, s);
-  MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "mc_scan_bwd: B/C quad relayout launch failed: %s", hipGetErrorString(e));
-
-  BwdArgs a;
-  a.batch = p->batch; a.dim = p->dim; a.seqlen = p->seqlen; a.dstate = p->dstate; a.n_groups = p->n_groups;
-  a.n_states = mc_scan_n_states(p->seqlen, S);
-  a.state_ratio = kS / S;
-  const int H = p->dim / p->n_groups;
-  a.nblk = (H + kRows - 1) / kRows;
-  a.total_blocks = p->batch * p->n_groups * a.nblk;
-  a.softplus = p->delta_softplus;
-  a.u_bs = p->u_batch_stride; a.u_ds = p->u_dim_stride;
-  a.dt_bs = p->delta_batch_stride; a.dt_ds = p->delta_dim_stride;
-  a.z_bs = p->z_batch_stride; a.z_ds = p->z_dim_stride;
-  a.go_bs = p->dout_batch_stride; a.go_ds = p->dout_dim_stride;
-  a.u = p->u; a.delta = p->delta; a.z = p->z; a.dout = p->dout;
-  a.A = p->A; a.bq = reinterpret_cast<const float*>(bq); a.D = p->D; a.delta_bias = p->delta_bias;
-  a.chunk_states = p->chunk_states;
-  a.du = p->du; a.ddelta = p->ddelta; a.dz = p->dz;
-  a.du_bs = p->du_batch_stride; a.du_ds = p->du_dim_stride;
-  a.ddt_bs = p->ddelta_batch_stride; a.ddt_ds = p->ddelta_dim_stride;
-  a.dz_bs = p->dz_batch_stride; a.dz_ds = p->dz_dim_stride;
-  a.slab_bc = reinterpret_cast<float*>(ws + w.slab_bc);
-  a.slab_a = reinterpret_cast<float*>(ws + w.slab_a);
-  a.slab_d = reinterpret_cast<float*>(ws + w.slab_d);
-  a.slab_bias = reinterpret_cast<float*>(ws + w.slab_bias);
-  a.rev_groups = dirs ? p->reverse_groups : 0; a.u_groups = dirs ? p->u_groups : 0;
-
-  const int ib = p->itype == MC_DTYPE_F32 ? 4 : 2;
-  bool aligned = vec_ok(p->u, p->u_batch_stride, p->u_dim_stride, 0, ib) &&
-                 vec_ok(p->delta, p->delta_batch_stride, p->delta_dim_stride, 0, ib) &&
-                 vec_ok(p->z, p->z_batch_stride, p->z_dim_stride, 0, ib) &&
-                 vec_ok(p->dout, p->dout_batch_stride, p->dout_dim_stride, 0, ib) &&
-                 vec_ok(p->du, p->du_batch_stride, p->du_dim_stride, 0, ib) &&
-                 vec_ok(p->ddelta, p->ddelta_batch_stride, p->ddelta_dim_stride, 0, ib) &&
-                 vec_ok(p->dz, p->dz_batch_stride, p->dz_dim_stride, 0, ib);
-  // the vector path addresses a workgroup's 64 rows with 32-bit byte offsets
-  auto span_ok = [&](const void* t, int64_t ds) __attribute__((always_inline)) {
-    return !t || ((int64_t)(kRows - 1) * (ds < 0 ? -ds : ds) + p->seqlen + kTC) * ib < ((int64_t)1 << 31);
-  };
-  const bool spans = span_ok(p->u, p->u_dim_stride) && span_ok(p->delta, p->delta_dim_stride) &&
-                     span_ok(p->z, p->z_dim_stride) && span_ok(p->dout, p->dout_dim_stride) &&
-                     span_ok(p->du, p->du_dim_stride) && span_ok(p->ddelta, p->ddelta_dim_stride) &&
-                     span_ok(p->dz, p->dz_dim_stride);
-  aligned = aligned && spans && (!dirs || p->seqlen % (16 / ib) == 0);   // mirrored blocks stay aligned
-  if (p->itype == MC_DTYPE_F32) rc = launch_bwd_t<float>(a, aligned, s);
-  else if (p->itype == MC_DTYPE_BF16) rc = launch_bwd_t<bf16_t>(a, aligned, s);
-  else rc = launch_bwd_t<f16_t>(a, aligned, s);
-  if (rc) return rc;
-  if (p->wtype == MC_DTYPE_F32) launch_reduce_t<float>(a, p, p->dB, p->dC, p->dA, p->dD, p->ddelta_bias, s);
-  else if (p->wtype == MC_DTYPE_BF16) launch_reduce_t<bf16_t>(a, p, p->dB, p->dC, p->dA, p->dD, p->ddelta_bias, s);
-  else launch_reduce_t<f16_t>(a, p, p->dB, p->dC, p->dA, p->dD, p->ddelta_bias, s);
-  e = hipGetLastError();
-  MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "mc_scan_bwd: reduce launch failed: %s", hipGetErrorString(e));
-  return MC_OK;
+  return launch_reduce(p, pl.slabs, pl.rows, s);
 }

@@ -38,9 +38,7 @@
 namespace mc {
 namespace scan {
 
-constexpr int kQW = 4;            // waves per workgroup
-constexpr int kQCh = 32;          // channels per wave
-constexpr int kQN = 16;           // dstate
+// kQW = 4 waves per workgroup, kQCh = 32 channels per wave, kQN = 16 states: scan_common.h
 constexpr int kQP = 4;            // state pairs per lane
 constexpr int kQT = 8;            // positions per sub-tile
 constexpr int kQSub = kS / kQT;   // sub-tiles per chunk
@@ -592,75 +590,18 @@ size_t bwd_pair_lds_bytes() {
 }
 static_assert(2 * (2 * kS * 2 * kQP * 16 + kQW * kS * 2 * kQN * 4 + kQW * (kQSub - 1) * 2 * 64 * 16 + kQW * 4 * kStageArrayBytes) <=
               160 * 1024, "two workgroups per CU");
-int bwd_pair_nblk(int H) { return (H + kQCh * kQW - 1) / (kQCh * kQW); }
 
-// Eligibility (the host has validated shapes; strides in elements).
-bool bwd_pair_ok(const mc_scan_bwd_params* p) {
-  const int ib = p->itype == MC_DTYPE_F32 ? 4 : 2;
-  const int wb = p->wtype == MC_DTYPE_F32 ? 4 : 2;
-  if (ib != 2 || p->wtype != p->itype || p->dstate != kQN || p->seqlen % 8 || p->reverse_groups || p->u_groups)
-    return false;
-  auto rows = [&](const void* t, int64_t bs, int64_t ds) {
-    return !t || (aligned16(t) && bs % 8 == 0 && ds % 8 == 0 &&
-                  ((int64_t)(kQCh * kQW - 1) * (ds < 0 ? -ds : ds) + p->seqlen) * 2 < ((int64_t)1 << 31));
-  };
-  auto bc = [&](const void* t, int64_t bs, int64_t gs, int64_t ns) {
-    const int64_t v = 16 / wb;
-    return aligned16(t) && bs % v == 0 && gs % v == 0 && ns % v == 0 && ns >= 0 &&
-           (15 * ns + p->seqlen) * wb < ((int64_t)1 << 31);
-  };
-  return rows(p->u, p->u_batch_stride, p->u_dim_stride) &&
-         rows(p->delta, p->delta_batch_stride, p->delta_dim_stride) &&
-         rows(p->z, p->z_batch_stride, p->z_dim_stride) && rows(p->dout, p->dout_batch_stride, p->dout_dim_stride) &&
-         rows(p->du, p->du_batch_stride, p->du_dim_stride) &&
-         rows(p->ddelta, p->ddelta_batch_stride, p->ddelta_dim_stride) &&
-         rows(p->dz, p->dz_batch_stride, p->dz_dim_stride) &&
-         bc(p->B, p->B_batch_stride, p->B_group_stride, p->B_dstate_stride) &&
-         bc(p->C, p->C_batch_stride, p->C_group_stride, p->C_dstate_stride) &&
-         (int64_t)kQCh * kQW * mc_scan_n_states(p->seqlen, p->state_interval) * kQN * 4 < ((int64_t)1 << 31);
-}
-
-template <typename TI>
-static void launch_pair_t(const BwdPairArgs& a, bool sp, bool zy, hipStream_t s) {
-  const size_t lds = bwd_pair_lds_bytes();
-  const dim3 grid(a.total_blocks), block(64 * kQW);
-  if (a.state_ratio != 1) {
-    if (sp && zy) hipLaunchKernelGGL((scan_bwd_pair_kernel<TI, true, true, true>), grid, block, lds, s, a);
-    else if (sp) hipLaunchKernelGGL((scan_bwd_pair_kernel<TI, true, false, true>), grid, block, lds, s, a);
-    else if (zy) hipLaunchKernelGGL((scan_bwd_pair_kernel<TI, false, true, true>), grid, block, lds, s, a);
-    else hipLaunchKernelGGL((scan_bwd_pair_kernel<TI, false, false, true>), grid, block, lds, s, a);
-    return;
-  }
-  if (sp && zy) hipLaunchKernelGGL((scan_bwd_pair_kernel<TI, true, true, false>), grid, block, lds, s, a);
-  else if (sp) hipLaunchKernelGGL((scan_bwd_pair_kernel<TI, true, false, false>), grid, block, lds, s, a);
-  else if (zy) hipLaunchKernelGGL((scan_bwd_pair_kernel<TI, false, true, false>), grid, block, lds, s, a);
-  else hipLaunchKernelGGL((scan_bwd_pair_kernel<TI, false, false, false>), grid, block, lds, s, a);
-}
-
-void launch_bwd_pair(const mc_scan_bwd_params* p, float* slab_bc, float* slab_a, float* slab_d, float* slab_bias,
-                     int nblk, hipStream_t s) {
+// A call plan_bwd (scan_bwd.hip) found eligible: one workgroup and one dB / dC slab per kQCh * kQW channels.
+void launch_bwd_pair(const mc_scan_bwd_params* p, const BwdSlabs& w, hipStream_t s) {
   BwdPairArgs a;
-  a.batch = p->batch; a.dim = p->dim; a.seqlen = p->seqlen; a.n_groups = p->n_groups;
-  a.n_states = mc_scan_n_states(p->seqlen, p->state_interval);
-  a.state_ratio = p->state_interval == kFineS ? kS / kFineS : 1;
-  a.nblk = nblk;
-  a.total_blocks = p->batch * p->n_groups * nblk;
-  a.u_bs = p->u_batch_stride; a.u_ds = p->u_dim_stride;
-  a.dt_bs = p->delta_batch_stride; a.dt_ds = p->delta_dim_stride;
-  a.z_bs = p->z_batch_stride; a.z_ds = p->z_dim_stride;
-  a.go_bs = p->dout_batch_stride; a.go_ds = p->dout_dim_stride;
-  a.du_bs = p->du_batch_stride; a.du_ds = p->du_dim_stride;
-  a.ddt_bs = p->ddelta_batch_stride; a.ddt_ds = p->ddelta_dim_stride;
-  a.dz_bs = p->dz_batch_stride; a.dz_ds = p->dz_dim_stride;
+  fill_bwd_args(a, p, w, kQCh * kQW);
+  a.B = p->B; a.C = p->C;
   a.B_bs = p->B_batch_stride; a.B_gs = p->B_group_stride; a.B_ns = p->B_dstate_stride;
   a.C_bs = p->C_batch_stride; a.C_gs = p->C_group_stride; a.C_ns = p->C_dstate_stride;
-  a.u = p->u; a.delta = p->delta; a.z = p->z; a.dout = p->dout; a.B = p->B; a.C = p->C;
-  a.A = p->A; a.D = p->D; a.delta_bias = p->delta_bias; a.chunk_states = p->chunk_states;
-  a.du = p->du; a.ddelta = p->ddelta; a.dz = p->dz;
-  a.slab_bc = slab_bc; a.slab_a = slab_a; a.slab_d = slab_d; a.slab_bias = slab_bias;
-  const bool sp = p->delta_softplus != 0, zy = p->z != nullptr;
-  if (p->itype == MC_DTYPE_BF16) launch_pair_t<bf16_t>(a, sp, zy, s);
-  else launch_pair_t<f16_t>(a, sp, zy, s);
+  const dim3 grid(a.total_blocks), block(64 * kQW);
+  MC_DISPATCH_T16(p->itype, MC_DISPATCH_BOOL(p->delta_softplus != 0, kSP, MC_DISPATCH_BOOL(
+      p->z != nullptr, kZ, MC_DISPATCH_BOOL(a.state_ratio != 1, kFine, hipLaunchKernelGGL(
+          (scan_bwd_pair_kernel<T, kSP, kZ, kFine>), grid, block, bwd_pair_lds_bytes(), s, a)))));
 }
 
 }  // namespace scan

@@ -135,8 +135,123 @@ struct FwdArgs {
   int state_interval;                // positions per saved state (pair kernel: 8 or 32; others 32)
 };
 
+// ---------------------------------------------------------------- host side
+// Channels per workgroup and dstate of the lane-pair kernels (scan_fwd_pair.hip, scan_bwd_pair.hip): the
+// plans size their 32-bit span checks, slabs and grids from these.
+constexpr int kPCh = 32;          // forward: channels per (one-wave) workgroup
+constexpr int kPN = 16;           // forward: dstate
+constexpr int kQW = 4;            // backward: waves per workgroup
+constexpr int kQCh = 32;          // backward: channels per wave
+constexpr int kQN = 16;           // backward: dstate
+
+// MC_DISPATCH_T / MC_DISPATCH_BOOL (mc_common.h) plus the scan's own axes: every launcher is one nested expression.
+#define MC_DISPATCH_T16(dtype, ...)                                 \
+  do {                                                              \
+    if ((dtype) == MC_DTYPE_BF16) { using T = bf16_t; __VA_ARGS__; } \
+    else { using T = f16_t; __VA_ARGS__; }                          \
+  } while (0)
+
+// padded dstate (8 / 16 / 32) as the compile-time constant kN
+#define MC_DISPATCH_NP(np, ...)                               \
+  do {                                                        \
+    if ((np) == 8) { constexpr int kN = 8; __VA_ARGS__; }      \
+    else if ((np) == 16) { constexpr int kN = 16; __VA_ARGS__; } \
+    else { constexpr int kN = 32; __VA_ARGS__; }               \
+  } while (0)
+
+// the three row modes of scan_fwd_kernel (0 element-wise, 1 aligned, 2 aligned and whole chunks) as kAl
+#define MC_DISPATCH_ALIGNED3(mode, ...)                        \
+  do {                                                         \
+    if ((mode) == 2) { constexpr int kAl = 2; __VA_ARGS__; }    \
+    else if ((mode) == 1) { constexpr int kAl = 1; __VA_ARGS__; } \
+    else { constexpr int kAl = 0; __VA_ARGS__; }                \
+  } while (0)
+
 int validate_common(int batch, int dim, int seqlen, int dstate, int n_groups, int itype, int wtype, const char* who);
-bool vec_ok(const void* p, int64_t s0, int64_t s1, int64_t s2, int elem_bytes);
+
+inline int elem_bytes(int dtype) { return dtype == MC_DTYPE_F32 ? 4 : 2; }
+
+// 16-B vector eligibility: pointer (null = absent, fine) aligned, strides in whole vectors
+inline bool vec_ok(const void* p, int64_t s0, int64_t s1, int64_t s2, int eb) {
+  const int64_t v = 16 / eb;
+  return p == nullptr || (aligned16(p) && s0 % v == 0 && s1 % v == 0 && s2 % v == 0);
+}
+
+// A (batch, dim, seqlen) row tensor, seqlen stride 1; p null = absent (passes every check).
+struct Rows {
+  const void* p;
+  int64_t bs, ds;
+};
+inline bool rows_vec_ok(const Rows& r, int eb) { return vec_ok(r.p, r.bs, r.ds, 0, eb); }
+// a workgroup addresses its `rows` rows (plus `tail` positions past the first element of the last row)
+// with 32-bit byte offsets
+inline bool rows_span32(const Rows& r, int rows, int64_t tail, int eb) {
+  return !r.p || ((int64_t)(rows - 1) * (r.ds < 0 ? -r.ds : r.ds) + tail) * eb < ((int64_t)1 << 31);
+}
+template <size_t kCount>
+inline bool all_vec_ok(const Rows (&t)[kCount], int eb) {
+  for (const Rows& r : t) if (!rows_vec_ok(r, eb)) return false;
+  return true;
+}
+template <size_t kCount>
+inline bool all_span32(const Rows (&t)[kCount], int rows, int64_t tail, int eb) {
+  for (const Rows& r : t) if (!rows_span32(r, rows, tail, eb)) return false;
+  return true;
+}
+// B / C as the pair kernels read them: 16-B aligned rows, strides in whole vectors, a group's dstate rows
+// ascending and within 32-bit byte offsets
+inline bool bc_rows_ok(const void* t, int64_t bs, int64_t gs, int64_t ns, int dstate, int seqlen, int eb) {
+  return vec_ok(t, bs, gs, ns, eb) && ns >= 0 && ((int64_t)(dstate - 1) * ns + seqlen) * eb < ((int64_t)1 << 31);
+}
+// what both pair kernels ask of a call beyond its row tensors
+template <typename Params>
+inline bool pair_shape_ok(const Params* p, int dstate) {
+  const int eb = elem_bytes(p->wtype);
+  return elem_bytes(p->itype) == 2 && p->wtype == p->itype && p->dstate == dstate && p->seqlen % 8 == 0 &&
+         p->reverse_groups == 0 && p->u_groups == 0 &&
+         bc_rows_ok(p->B, p->B_batch_stride, p->B_group_stride, p->B_dstate_stride, dstate, p->seqlen, eb) &&
+         bc_rows_ok(p->C, p->C_batch_stride, p->C_group_stride, p->C_dstate_stride, dstate, p->seqlen, eb);
+}
+
+inline bool has_dirs(int reverse_groups, int u_groups) { return reverse_groups != 0 || u_groups != 0; }
+// grouped directions, vector modes: a mirrored 16-B block is aligned only when seqlen is whole vectors
+inline bool dirs_vec_ok(bool dirs, int seqlen, int eb) { return !dirs || seqlen % (16 / eb) == 0; }
+
+template <typename Params>
+int check_dirs(const Params* p, const char* who) {
+  if (!has_dirs(p->reverse_groups, p->u_groups)) return MC_OK;
+  MC_CHECK(!p->z && p->u_groups >= 0 && p->u_groups <= p->n_groups && p->n_groups <= 31 &&
+               (p->reverse_groups >> p->n_groups) == 0,
+           MC_ERR_SHAPE, "%s: reverse_groups / u_groups need no z, 0 <= u_groups <= n_groups <= 31 and "
+           "a mask within n_groups (got mask 0x%x, u_groups %d, n_groups %d)", who, p->reverse_groups, p->u_groups,
+           p->n_groups);
+  return MC_OK;
+}
+
+// The fields BwdArgs (scan_bwd.hip) and BwdPairArgs (scan_bwd_pair.hip) share, from validated params;
+// `rows`: channels per workgroup of the kernel the args are for.
+struct BwdSlabs {
+  float* bc; float* a; float* d; float* bias;   // partial sums in the workspace (layouts: BwdArgs)
+};
+template <typename Args>
+void fill_bwd_args(Args& a, const mc_scan_bwd_params* p, const BwdSlabs& w, int rows) {
+  a.batch = p->batch; a.dim = p->dim; a.seqlen = p->seqlen; a.n_groups = p->n_groups;
+  a.n_states = mc_scan_n_states(p->seqlen, p->state_interval);
+  a.state_ratio = p->state_interval == kFineS ? kS / kFineS : 1;
+  a.nblk = (p->dim / p->n_groups + rows - 1) / rows;
+  a.total_blocks = p->batch * p->n_groups * a.nblk;
+  a.u_bs = p->u_batch_stride; a.u_ds = p->u_dim_stride;
+  a.dt_bs = p->delta_batch_stride; a.dt_ds = p->delta_dim_stride;
+  a.z_bs = p->z_batch_stride; a.z_ds = p->z_dim_stride;
+  a.go_bs = p->dout_batch_stride; a.go_ds = p->dout_dim_stride;
+  a.du_bs = p->du_batch_stride; a.du_ds = p->du_dim_stride;
+  a.ddt_bs = p->ddelta_batch_stride; a.ddt_ds = p->ddelta_dim_stride;
+  a.dz_bs = p->dz_batch_stride; a.dz_ds = p->dz_dim_stride;
+  a.u = p->u; a.delta = p->delta; a.z = p->z; a.dout = p->dout;
+  a.A = p->A; a.D = p->D; a.delta_bias = p->delta_bias; a.chunk_states = p->chunk_states;
+  a.du = p->du; a.ddelta = p->ddelta; a.dz = p->dz;
+  a.slab_bc = w.bc; a.slab_a = w.a; a.slab_d = w.d; a.slab_bias = w.bias;
+}
 
 }  // namespace scan
 }  // namespace mc

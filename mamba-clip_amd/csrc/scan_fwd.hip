@@ -30,9 +30,8 @@
 namespace mc {
 namespace scan {
 
-// FwdArgs: scan_common.h
-bool fwd_pair_ok(const FwdArgs& a, bool aligned, int itype_bytes, int itype, int wtype);   // scan_fwd_pair.hip
-int launch_fwd_pair(const FwdArgs& a, int itype, hipStream_t s);
+// FwdArgs, the row checks and the dispatch macros: scan_common.h
+int launch_fwd_pair(const FwdArgs& a, int itype, hipStream_t s);   // scan_fwd_pair.hip
 
 // B/C as the recurrence consumes them: fp32, position-major, [b][g][l][2*kNp]
 // (B states 0..kNp-1 then C states; states >= dstate are zero).  Every lane of
@@ -102,54 +101,25 @@ __global__ __launch_bounds__(256) void bc_relayout_vec_kernel(const TW* __restri
   }
 }
 
-template <typename TW>
-static hipError_t launch_bc_relayout(const void* B, const void* C, int64_t B_bs, int64_t B_gs, int64_t B_ns,
-                                     int64_t C_bs, int64_t C_gs, int64_t C_ns, int batch, int G, int L, int dstate,
-                                     int rev, float* out, hipStream_t s) {
-  const int np = padded_dstate(dstate);
-  const TW* b = reinterpret_cast<const TW*>(B);
-  const TW* c = reinterpret_cast<const TW*>(C);
-  if constexpr (sizeof(TW) == 2) {
-    auto al = [](const void* p, int64_t s0, int64_t s1, int64_t s2) {
-      return aligned16(p) && s0 % 8 == 0 && s1 % 8 == 0 && s2 % 8 == 0;
-    };
-    if (rev == 0 && L % 8 == 0 && al(B, B_bs, B_gs, B_ns) && al(C, C_bs, C_gs, C_ns) && np >= 8) {
-      const int64_t tv = (int64_t)batch * G * (L / 8) * 2;
-      const int gv = (int)std::min<int64_t>((tv + 255) / 256, 16384);
-      if (np == 8)
-        hipLaunchKernelGGL((bc_relayout_vec_kernel<TW, 8>), gv, 256, 0, s, b, c, B_bs, B_gs, B_ns, C_bs, C_gs, C_ns,
-                           batch, G, L, dstate, out);
-      else if (np == 16)
-        hipLaunchKernelGGL((bc_relayout_vec_kernel<TW, 16>), gv, 256, 0, s, b, c, B_bs, B_gs, B_ns, C_bs, C_gs, C_ns,
-                           batch, G, L, dstate, out);
-      else
-        hipLaunchKernelGGL((bc_relayout_vec_kernel<TW, 32>), gv, 256, 0, s, b, c, B_bs, B_gs, B_ns, C_bs, C_gs, C_ns,
-                           batch, G, L, dstate, out);
-      return hipGetLastError();
-    }
+static hipError_t relayout_bc(const mc_scan_fwd_params* p, int rev, float* out, hipStream_t s) {
+  const int np = padded_dstate(p->dstate), batch = p->batch, G = p->n_groups, L = p->seqlen, dstate = p->dstate;
+  const int64_t B_bs = p->B_batch_stride, B_gs = p->B_group_stride, B_ns = p->B_dstate_stride;
+  const int64_t C_bs = p->C_batch_stride, C_gs = p->C_group_stride, C_ns = p->C_dstate_stride;
+  if (elem_bytes(p->wtype) == 2 && rev == 0 && L % 8 == 0 && vec_ok(p->B, B_bs, B_gs, B_ns, 2) &&
+      vec_ok(p->C, C_bs, C_gs, C_ns, 2)) {
+    const int64_t tv = (int64_t)batch * G * (L / 8) * 2;
+    const int gv = (int)std::min<int64_t>((tv + 255) / 256, 16384);
+    MC_DISPATCH_T16(p->wtype, MC_DISPATCH_NP(np, hipLaunchKernelGGL(
+        (bc_relayout_vec_kernel<T, kN>), gv, 256, 0, s, reinterpret_cast<const T*>(p->B),
+        reinterpret_cast<const T*>(p->C), B_bs, B_gs, B_ns, C_bs, C_gs, C_ns, batch, G, L, dstate, out)));
+    return hipGetLastError();
   }
   const int64_t total = (int64_t)batch * G * L * 2 * np;
   const int grid = (int)std::min<int64_t>((total + 255) / 256, 8192);
-  if (np == 8)
-    hipLaunchKernelGGL((bc_relayout_kernel<TW, 8>), grid, 256, 0, s, b, c, B_bs, B_gs, B_ns, C_bs, C_gs, C_ns, batch,
-                       G, L, dstate, rev, out);
-  else if (np == 16)
-    hipLaunchKernelGGL((bc_relayout_kernel<TW, 16>), grid, 256, 0, s, b, c, B_bs, B_gs, B_ns, C_bs, C_gs, C_ns,
-                       batch, G, L, dstate, rev, out);
-  else
-    hipLaunchKernelGGL((bc_relayout_kernel<TW, 32>), grid, 256, 0, s, b, c, B_bs, B_gs, B_ns, C_bs, C_gs, C_ns,
-                       batch, G, L, dstate, rev, out);
+  MC_DISPATCH_T(p->wtype, MC_DISPATCH_NP(np, hipLaunchKernelGGL(
+      (bc_relayout_kernel<T, kN>), grid, 256, 0, s, reinterpret_cast<const T*>(p->B),
+      reinterpret_cast<const T*>(p->C), B_bs, B_gs, B_ns, C_bs, C_gs, C_ns, batch, G, L, dstate, rev, out)));
   return hipGetLastError();
-}
-
-static hipError_t relayout_bc(int wtype, const void* B, const void* C, int64_t B_bs, int64_t B_gs, int64_t B_ns,
-                              int64_t C_bs, int64_t C_gs, int64_t C_ns, int batch, int G, int L, int dstate,
-                              int rev, float* out, hipStream_t s) {
-  if (wtype == MC_DTYPE_F32)
-    return launch_bc_relayout<float>(B, C, B_bs, B_gs, B_ns, C_bs, C_gs, C_ns, batch, G, L, dstate, rev, out, s);
-  if (wtype == MC_DTYPE_BF16)
-    return launch_bc_relayout<bf16_t>(B, C, B_bs, B_gs, B_ns, C_bs, C_gs, C_ns, batch, G, L, dstate, rev, out, s);
-  return launch_bc_relayout<f16_t>(B, C, B_bs, B_gs, B_ns, C_bs, C_gs, C_ns, batch, G, L, dstate, rev, out, s);
 }
 
 // LDS row of one channel for one chunk: kT / VI blocks; block k = {u vector k
@@ -745,34 +715,7 @@ __global__ __launch_bounds__(kRows, 3) void scan_fwd_mc_kernel(const FwdArgs a) 
   }
 }
 
-// ------------------------------------------------------------------ host dispatch
-template <typename TI, int kN>
-static void launch_fwd_mc(const FwdArgs& a, bool aligned, hipStream_t s) {
-  const size_t lds = (size_t)kRows * RowLayoutP<TI>::kStride;
-  const dim3 grid(a.total_blocks), block(kRows);
-  if (aligned && a.softplus) hipLaunchKernelGGL((scan_fwd_mc_kernel<TI, kN, true, true>), grid, block, lds, s, a);
-  else if (aligned) hipLaunchKernelGGL((scan_fwd_mc_kernel<TI, kN, true, false>), grid, block, lds, s, a);
-  else if (a.softplus) hipLaunchKernelGGL((scan_fwd_mc_kernel<TI, kN, false, true>), grid, block, lds, s, a);
-  else hipLaunchKernelGGL((scan_fwd_mc_kernel<TI, kN, false, false>), grid, block, lds, s, a);
-}
-
-template <typename TI, int kN>
-static void launch_fwd_lds(const FwdArgs& a, bool aligned, hipStream_t s) {
-  const size_t lds = (size_t)kRows * RowLayout<TI>::kStride + (size_t)kT * 2 * kN * 4;
-  const dim3 grid(a.total_blocks), block(kRows);
-  auto fits = [&](int64_t ds) {
-    return ((int64_t)(kRows - 1) * (ds < 0 ? -ds : ds) + a.seqlen) * (int64_t)sizeof(TI) < ((int64_t)1 << 31);
-  };
-  const bool span32 = fits(a.o_ds) && fits(a.u_ds) && fits(a.dt_ds) && (!a.z || fits(a.z_ds)) &&
-                      (!a.out_y || fits(a.y_ds));
-#define MC_FWD_LAUNCH(AL, SP) hipLaunchKernelGGL((scan_fwd_kernel<TI, kN, AL, SP>), grid, block, lds, s, a)
-  const bool sp = a.softplus != 0;
-  if (aligned && a.seqlen % kT == 0 && span32) { if (sp) MC_FWD_LAUNCH(2, true); else MC_FWD_LAUNCH(2, false); }
-  else if (aligned) { if (sp) MC_FWD_LAUNCH(1, true); else MC_FWD_LAUNCH(1, false); }
-  else { if (sp) MC_FWD_LAUNCH(0, true); else MC_FWD_LAUNCH(0, false); }
-#undef MC_FWD_LAUNCH
-}
-
+// ------------------------------------------------------------------ host: plan and dispatch
 // Kernel choice, measured on MI355X (ms, bf16, z, softplus):
 //                                         C4 64x3072x4096   C2 256x1536x80
 //   scan_fwd_kernel (kG 4, LDS B/C, 2 w/SIMD)     3.17 (r01: 3.35) 0.204
@@ -787,21 +730,104 @@ static void launch_fwd_lds(const FwdArgs& a, bool aligned, hipStream_t s) {
 // sequences the grid is many short-lived waves and the SGPR-fed kernel wins;
 // with long ones the LDS-staged kernel's deeper prefetch wins.  Grouped directions
 // (per-group addressing) live in the LDS-staged kernel only.
-template <typename TI, int kN>
-static void launch_fwd_n(const FwdArgs& a, bool aligned, bool dirs, hipStream_t s) {
-  if (a.seqlen <= 512 && !dirs) launch_fwd_mc<TI, kN>(a, aligned, s);
-  else launch_fwd_lds<TI, kN>(a, aligned, s);
+//
+// Everything mc_scan_fwd does for a call, decided in one place; the queries read the same plan.
+struct FwdPlan {
+  int family = MC_SCAN_KERNEL_NONE;   // MC_SCAN_KERNEL_*; NONE: nothing to launch
+  bool mc = false;                    // general kernels: scan_fwd_mc_kernel (else the LDS-staged scan_fwd_kernel)
+  int aligned = 0;                    // general kernels: row mode 0 / 1 / 2 (scan_fwd_mc_kernel: 0 / 1)
+  int state_interval = kS;            // the interval the call saves states with
+  FwdArgs a;
+};
+static_assert(kS == kT, "the pair kernel saves its default states at the ends of the forward's tiles");
+
+// FwdArgs of a planned call; `rows`: channels per workgroup of the chosen kernel.  The workspace is the
+// relaid B / C of the general kernels (the pair kernel reads the rows as given).
+static void fill_fwd_args(const mc_scan_fwd_params* p, const FwdPlan& pl, int rows, FwdArgs& a) {
+  const bool dirs = has_dirs(p->reverse_groups, p->u_groups);
+  a.batch = p->batch; a.dim = p->dim; a.seqlen = p->seqlen; a.dstate = p->dstate; a.n_groups = p->n_groups;
+  a.n_chunks = (p->seqlen + kT - 1) / kT;
+  a.n_states = mc_scan_n_states(p->seqlen, pl.state_interval);
+  a.nblk = (int)(((int64_t)p->dim / p->n_groups + rows - 1) / rows);   // 64-bit: no trap on unvalidated params
+  a.total_blocks = p->batch * p->n_groups * a.nblk;
+  a.softplus = p->delta_softplus;
+  a.u_bs = p->u_batch_stride; a.u_ds = p->u_dim_stride;
+  a.dt_bs = p->delta_batch_stride; a.dt_ds = p->delta_dim_stride;
+  a.z_bs = p->z_batch_stride; a.z_ds = p->z_dim_stride;
+  a.o_bs = p->out_batch_stride; a.o_ds = p->out_dim_stride;
+  a.u = p->u; a.delta = p->delta; a.A = p->A; a.bct = reinterpret_cast<const float*>(p->workspace);
+  a.D = p->D; a.z = p->z; a.delta_bias = p->delta_bias;
+  a.out = p->out; a.chunk_states = p->chunk_states; a.last_state = p->last_state;
+  a.out_y = p->z ? p->out_y : nullptr; a.y_bs = p->out_y_batch_stride; a.y_ds = p->out_y_dim_stride;
+  a.rev_groups = dirs ? p->reverse_groups : 0; a.u_groups = dirs ? p->u_groups : 0;
+  a.B = p->B; a.C = p->C;
+  a.B_bs = p->B_batch_stride; a.B_gs = p->B_group_stride; a.B_ns = p->B_dstate_stride;
+  a.C_bs = p->C_batch_stride; a.C_gs = p->C_group_stride; a.C_ns = p->C_dstate_stride;
+  a.state_interval = pl.state_interval;
 }
 
-template <typename TI>
-static int launch_fwd_t(const FwdArgs& a, bool aligned, bool dirs, hipStream_t s) {
-  const int np = padded_dstate(a.dstate);
-  if (np == 8) launch_fwd_n<TI, 8>(a, aligned, dirs, s);
-  else if (np == 16) launch_fwd_n<TI, 16>(a, aligned, dirs, s);
-  else launch_fwd_n<TI, 32>(a, aligned, dirs, s);
-  const hipError_t e = hipGetLastError();
-  MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "mc_scan_fwd: launch failed: %s", hipGetErrorString(e));
+// The choice: what a call with these params runs.  It reads shapes, strides and pointer alignment only,
+// reports no error and touches nothing else, so the queries answer from it for any params, valid or not;
+// n_groups == 0 (no channels per group to divide into) leaves the defaults, NONE / kS.
+static void choose_fwd(const mc_scan_fwd_params* p, FwdPlan& pl) {
+  pl = FwdPlan{};
+  if (p->n_groups == 0) return;
+  const bool empty = p->batch == 0 || p->seqlen == 0, dirs = has_dirs(p->reverse_groups, p->u_groups);
+  const int ib = elem_bytes(p->itype);
+  const Rows rows[] = {{p->u, p->u_batch_stride, p->u_dim_stride},
+                       {p->delta, p->delta_batch_stride, p->delta_dim_stride},
+                       {p->z, p->z_batch_stride, p->z_dim_stride},
+                       {p->out, p->out_batch_stride, p->out_dim_stride},
+                       {p->z ? p->out_y : nullptr, p->out_y_batch_stride, p->out_y_dim_stride}};
+  const bool aligned = all_vec_ok(rows, ib);
+  // 16-bit rows, N = 16: state-split lane pairs (scan_fwd_pair.hip; C4 2.78 vs 3.22 ms, C2 training
+  // forward 0.166 vs 0.183 ms per layer).  It reads B / C rows itself: no relayout pre-pass.
+  const bool pair = pair_shape_ok(p, kPN) && aligned && all_span32(rows, kPCh, p->seqlen, ib);
+  pl.family = empty ? MC_SCAN_KERNEL_NONE
+                    : dirs ? MC_SCAN_KERNEL_DIRS : pair ? MC_SCAN_KERNEL_PAIR : MC_SCAN_KERNEL_GENERIC;
+  pl.state_interval = pair && p->state_interval == kFineS ? kFineS : kS;   // the others save every kS
+  if (!pair) {
+    pl.mc = p->seqlen <= 512 && !dirs;
+    const bool whole = !pl.mc && p->seqlen % kT == 0 && all_span32(rows, kRows, p->seqlen, ib);
+    pl.aligned = !(aligned && dirs_vec_ok(dirs, p->seqlen, ib)) ? 0 : whole ? 2 : 1;
+  }
+  fill_fwd_args(p, pl, pair ? kPCh : kRows, pl.a);
+}
+
+// The checks of a call, in the ABI's order, around the choice.
+static int plan_fwd(const mc_scan_fwd_params* p, FwdPlan& pl) {
+  MC_CHECK(p != nullptr, MC_ERR_INVALID, "mc_scan_fwd: null params");
+  choose_fwd(p, pl);
+  MC_TRY(validate_common(p->batch, p->dim, p->seqlen, p->dstate, p->n_groups, p->itype, p->wtype, "mc_scan_fwd"));
+  if (pl.family == MC_SCAN_KERNEL_NONE) return MC_OK;   // nothing to scan
+  MC_CHECK(p->u && p->delta && p->A && p->B && p->C && p->out, MC_ERR_INVALID,
+           "mc_scan_fwd: u, delta, A, B, C and out must be non-null");
+  const size_t need = bct_bytes(p->batch, p->seqlen, p->dstate, p->n_groups);
+  MC_CHECK(p->workspace && p->workspace_bytes >= need && aligned16(p->workspace), MC_ERR_WORKSPACE,
+           "mc_scan_fwd: workspace must be >= %zu bytes and 16-B aligned (got %zu)", need, p->workspace_bytes);
+  MC_TRY(check_dirs(p, "mc_scan_fwd"));
+  MC_CHECK(p->state_interval == 0 || p->state_interval == kS ||
+               (p->state_interval == kFineS && pl.family == MC_SCAN_KERNEL_PAIR),
+           MC_ERR_SHAPE,
+           "mc_scan_fwd: state_interval %d: 0 / %d, or %d on the pair kernel's shapes (mc_scan_fwd_state_interval)",
+           p->state_interval, kS, kFineS);
   return MC_OK;
+}
+
+static int launch_fwd_generic(const FwdPlan& pl, int itype, hipStream_t s) {
+  const FwdArgs& a = pl.a;
+  const dim3 grid(a.total_blocks), block(kRows);
+  const int np = padded_dstate(a.dstate);
+  if (pl.mc)
+    MC_DISPATCH_T(itype, MC_DISPATCH_NP(np, MC_DISPATCH_BOOL(pl.aligned != 0, kAl, MC_DISPATCH_BOOL(
+        a.softplus != 0, kSP, hipLaunchKernelGGL((scan_fwd_mc_kernel<T, kN, kAl, kSP>), grid, block,
+                                                 (size_t)kRows * RowLayoutP<T>::kStride, s, a)))));
+  else
+    MC_DISPATCH_T(itype, MC_DISPATCH_NP(np, MC_DISPATCH_ALIGNED3(pl.aligned, MC_DISPATCH_BOOL(
+        a.softplus != 0, kSP, hipLaunchKernelGGL((scan_fwd_kernel<T, kN, kAl, kSP>), grid, block,
+                                                 (size_t)kRows * RowLayout<T>::kStride + (size_t)kT * 2 * kN * 4, s,
+                                                 a)))));
+  return check_launch("mc_scan_fwd");
 }
 
 int validate_common(int batch, int dim, int seqlen, int dstate, int n_groups, int itype, int wtype, const char* who) {
@@ -814,11 +840,6 @@ int validate_common(int batch, int dim, int seqlen, int dstate, int n_groups, in
   MC_CHECK(itype >= MC_DTYPE_F32 && itype <= MC_DTYPE_F16, MC_ERR_DTYPE, "%s: bad input dtype %d", who, itype);
   MC_CHECK(wtype >= MC_DTYPE_F32 && wtype <= MC_DTYPE_F16, MC_ERR_DTYPE, "%s: bad weight dtype %d", who, wtype);
   return MC_OK;
-}
-
-bool vec_ok(const void* p, int64_t s0, int64_t s1, int64_t s2, int elem_bytes) {
-  const int64_t v = 16 / elem_bytes;
-  return p == nullptr || (aligned16(p) && s0 % v == 0 && s1 % v == 0 && s2 % v == 0);
 }
 
 }  // namespace scan
@@ -843,102 +864,30 @@ extern "C" size_t mc_scan_fwd_workspace_bytes(int32_t batch, int32_t seqlen, int
   return bct_bytes(batch, seqlen, dstate, n_groups);
 }
 
-static bool fill_fwd_args(const mc_scan_fwd_params* p, FwdArgs& a, bool& aligned);
-
 extern "C" int mc_scan_fwd(const mc_scan_fwd_params* p, void* stream) {
-  MC_CHECK(p != nullptr, MC_ERR_INVALID, "mc_scan_fwd: null params");
-  int rc = validate_common(p->batch, p->dim, p->seqlen, p->dstate, p->n_groups, p->itype, p->wtype, "mc_scan_fwd");
-  if (rc) return rc;
+  FwdPlan pl;
+  MC_TRY(plan_fwd(p, pl));
   hipStream_t s = (hipStream_t)stream;
-  if (p->batch == 0 || p->seqlen == 0) {
-    // nothing to scan; a zero-length sequence leaves the state at zero
+  if (pl.family == MC_SCAN_KERNEL_NONE) {
+    // a zero-length sequence leaves the state at zero
     if (p->last_state && p->batch > 0)
       (void)hipMemsetAsync(p->last_state, 0, (size_t)p->batch * p->dim * p->dstate * 4, s);
     return MC_OK;
   }
-  MC_CHECK(p->u && p->delta && p->A && p->B && p->C && p->out, MC_ERR_INVALID,
-           "mc_scan_fwd: u, delta, A, B, C and out must be non-null");
-  const size_t need = bct_bytes(p->batch, p->seqlen, p->dstate, p->n_groups);
-  MC_CHECK(p->workspace && p->workspace_bytes >= need && aligned16(p->workspace), MC_ERR_WORKSPACE,
-           "mc_scan_fwd: workspace must be >= %zu bytes and 16-B aligned (got %zu)", need, p->workspace_bytes);
-
-  const bool dirs = p->reverse_groups != 0 || p->u_groups != 0;
-  if (dirs) {
-    MC_CHECK(!p->z && p->u_groups >= 0 && p->u_groups <= p->n_groups && p->n_groups <= 31 &&
-                 (p->reverse_groups >> p->n_groups) == 0,
-             MC_ERR_SHAPE, "mc_scan_fwd: reverse_groups / u_groups need no z, 0 <= u_groups <= n_groups <= 31 and "
-             "a mask within n_groups (got mask 0x%x, u_groups %d, n_groups %d)", p->reverse_groups, p->u_groups,
-             p->n_groups);
-  }
-  FwdArgs a;
-  bool aligned = false;
-  const bool pair = fill_fwd_args(p, a, aligned);
-  const int ib = p->itype == MC_DTYPE_F32 ? 4 : 2;
-  MC_CHECK(p->state_interval == 0 || p->state_interval == kS || (p->state_interval == kFineS && pair), MC_ERR_SHAPE,
-           "mc_scan_fwd: state_interval %d: 0 / %d, or %d on the pair kernel's shapes (mc_scan_fwd_state_interval)",
-           p->state_interval, kS, kFineS);
-  // 16-bit rows, N = 16: state-split lane pairs (scan_fwd_pair.hip; C4 2.78 vs 3.22 ms, C2 training
-  // forward 0.166 vs 0.183 ms per layer).  It reads B / C rows itself: no relayout pre-pass.
-  if (pair) return launch_fwd_pair(a, p->itype, s);
-  hipError_t e = relayout_bc(p->wtype, p->B, p->C, p->B_batch_stride, p->B_group_stride, p->B_dstate_stride,
-                             p->C_batch_stride, p->C_group_stride, p->C_dstate_stride, p->batch, p->n_groups,
-                             p->seqlen, p->dstate, dirs ? p->reverse_groups : 0,
-                             reinterpret_cast<float*>(p->workspace), s);
+  if (pl.family == MC_SCAN_KERNEL_PAIR) return launch_fwd_pair(pl.a, p->itype, s);
+  const hipError_t e = relayout_bc(p, pl.a.rev_groups, reinterpret_cast<float*>(p->workspace), s);
   MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "mc_scan_fwd: B/C relayout launch failed: %s", hipGetErrorString(e));
-  // grouped directions, vector modes: a mirrored 16-B block is aligned only when seqlen % VI == 0
-  const bool al = aligned && (!dirs || p->seqlen % (16 / ib) == 0);
-  if (p->itype == MC_DTYPE_F32) return launch_fwd_t<float>(a, al, dirs, s);
-  if (p->itype == MC_DTYPE_BF16) return launch_fwd_t<bf16_t>(a, al, dirs, s);
-  return launch_fwd_t<f16_t>(a, al, dirs, s);
+  return launch_fwd_generic(pl, p->itype, s);
 }
 
 extern "C" int32_t mc_scan_fwd_kernel(const mc_scan_fwd_params* p) {
-  if (!p || p->batch == 0 || p->seqlen == 0) return MC_SCAN_KERNEL_NONE;
-  if (p->reverse_groups != 0 || p->u_groups != 0) return MC_SCAN_KERNEL_DIRS;
-  FwdArgs a;
-  bool aligned = false;
-  return fill_fwd_args(p, a, aligned) ? MC_SCAN_KERNEL_PAIR : MC_SCAN_KERNEL_GENERIC;
+  FwdPlan pl;
+  if (p) choose_fwd(p, pl);
+  return pl.family;
 }
 
 extern "C" int32_t mc_scan_fwd_state_interval(const mc_scan_fwd_params* p) {
-  if (!p || p->state_interval != kFineS) return kS;
-  FwdArgs a;
-  bool aligned = false;
-  return fill_fwd_args(p, a, aligned) ? kFineS : kS;
-}
-
-// FwdArgs from validated params; returns whether the pair kernel takes the call.  a.state_interval is
-// the fine interval only when requested and the pair kernel runs (the others save every kS).
-static bool fill_fwd_args(const mc_scan_fwd_params* p, FwdArgs& a, bool& aligned) {
-  const bool dirs = p->reverse_groups != 0 || p->u_groups != 0;
-  a.batch = p->batch; a.dim = p->dim; a.seqlen = p->seqlen; a.dstate = p->dstate; a.n_groups = p->n_groups;
-  a.n_chunks = (p->seqlen + kT - 1) / kT;
-  a.n_states = mc_scan_n_chunks(p->seqlen);
-  const int H = p->dim / p->n_groups;
-  a.nblk = (H + kRows - 1) / kRows;
-  a.total_blocks = p->batch * p->n_groups * a.nblk;
-  a.softplus = p->delta_softplus;
-  a.u_bs = p->u_batch_stride; a.u_ds = p->u_dim_stride;
-  a.dt_bs = p->delta_batch_stride; a.dt_ds = p->delta_dim_stride;
-  a.z_bs = p->z_batch_stride; a.z_ds = p->z_dim_stride;
-  a.o_bs = p->out_batch_stride; a.o_ds = p->out_dim_stride;
-  a.u = p->u; a.delta = p->delta; a.A = p->A; a.bct = reinterpret_cast<const float*>(p->workspace);
-  a.D = p->D; a.z = p->z; a.delta_bias = p->delta_bias;
-  a.out = p->out; a.chunk_states = p->chunk_states; a.last_state = p->last_state;
-  a.out_y = p->z ? p->out_y : nullptr; a.y_bs = p->out_y_batch_stride; a.y_ds = p->out_y_dim_stride;
-  a.rev_groups = dirs ? p->reverse_groups : 0; a.u_groups = dirs ? p->u_groups : 0;
-  a.B = p->B; a.C = p->C;
-  a.B_bs = p->B_batch_stride; a.B_gs = p->B_group_stride; a.B_ns = p->B_dstate_stride;
-  a.C_bs = p->C_batch_stride; a.C_gs = p->C_group_stride; a.C_ns = p->C_dstate_stride;
-
-  const int ib = p->itype == MC_DTYPE_F32 ? 4 : 2;
-  aligned = vec_ok(p->u, p->u_batch_stride, p->u_dim_stride, 0, ib) &&
-            vec_ok(p->delta, p->delta_batch_stride, p->delta_dim_stride, 0, ib) &&
-            vec_ok(p->z, p->z_batch_stride, p->z_dim_stride, 0, ib) &&
-            vec_ok(p->out, p->out_batch_stride, p->out_dim_stride, 0, ib) &&
-            vec_ok(a.out_y, a.y_bs, a.y_ds, 0, ib);
-  const bool pair = !dirs && fwd_pair_ok(a, aligned, ib, p->itype, p->wtype);
-  a.state_interval = (pair && p->state_interval == kFineS) ? kFineS : kS;
-  a.n_states = mc_scan_n_states(p->seqlen, a.state_interval);
-  return pair;
+  FwdPlan pl;
+  if (p) choose_fwd(p, pl);
+  return pl.state_interval;
 }

@@ -32,8 +32,7 @@
 namespace mc {
 namespace scan {
 
-constexpr int kPCh = 32;   // channels per wave
-constexpr int kPN = 16;    // dstate
+// kPCh = 32 channels per wave, kPN = 16 states: scan_common.h
 constexpr int kPH = 8;     // states per lane
 constexpr int kPG = 4;     // positions per recurrence group (32 B of {dt, du} per row)
 // Tried, slower (git history, profiles/r04/scan_fwd_exp_poly_ab.txt): decays of one or two of the four
@@ -304,46 +303,17 @@ __global__ __launch_bounds__(64, 3) void scan_fwd_pair_kernel(const FwdArgs a) {
   }
 }
 
-// Eligibility of the pair kernel for a (validated) forward call.
-bool fwd_pair_ok(const FwdArgs& a, bool aligned, int itype_bytes, int itype, int wtype) {
-  auto fits = [&](int64_t ds) {
-    return ((int64_t)(kPCh - 1) * (ds < 0 ? -ds : ds) + a.seqlen) * itype_bytes < ((int64_t)1 << 31);
-  };
-  auto bc = [&](const void* t, int64_t bs, int64_t gs, int64_t ns) {   // 16-bit rows, 16-B aligned, 32-bit spans
-    return aligned16(t) && bs % 8 == 0 && gs % 8 == 0 && ns % 8 == 0 && ns >= 0 && (15 * ns + a.seqlen) * 2 < ((int64_t)1 << 31);
-  };
-  return itype_bytes == 2 && wtype == itype && aligned && a.dstate == kPN && a.seqlen % 8 == 0 && kS == kT &&
-         a.rev_groups == 0 && a.u_groups == 0 && fits(a.u_ds) && fits(a.dt_ds) && fits(a.o_ds) &&
-         (!a.z || fits(a.z_ds)) && (!a.out_y || fits(a.y_ds)) && bc(a.B, a.B_bs, a.B_gs, a.B_ns) &&
-         bc(a.C, a.C_bs, a.C_gs, a.C_ns);
-}
-
-template <typename TI>
-static int launch_pair_t(const FwdArgs& a0, hipStream_t s) {
-  FwdArgs a = a0;
-  const int H = a.dim / a.n_groups;
-  a.nblk = (H + kPCh - 1) / kPCh;
-  a.total_blocks = a.batch * a.n_groups * a.nblk;
-  const size_t lds = (size_t)PairLayout<TI>::kRowBytes + PairLayout<TI>::kBCBytes;
-  const dim3 grid(a.total_blocks), block(64);
-  if (a.chunk_states && a.state_interval == kFineS) {   // training forward saving fine states
-    if (a.softplus) hipLaunchKernelGGL((scan_fwd_pair_kernel<TI, true, true>), grid, block, lds, s, a);
-    else hipLaunchKernelGGL((scan_fwd_pair_kernel<TI, false, true>), grid, block, lds, s, a);
-  } else {
-    if (a.softplus) hipLaunchKernelGGL((scan_fwd_pair_kernel<TI, true, false>), grid, block, lds, s, a);
-    else hipLaunchKernelGGL((scan_fwd_pair_kernel<TI, false, false>), grid, block, lds, s, a);
-  }
-  const hipError_t e = hipGetLastError();
-  MC_CHECK(e == hipSuccess, MC_ERR_LAUNCH, "mc_scan_fwd: launch failed: %s", hipGetErrorString(e));
-  return MC_OK;
-}
-
 // Measured alternatives (interleaved on one box, C4 ms; the variants are in git history):
 // median softplus 2.82, the same at 4 waves/SIMD (spills) 3.59, log1p softplus 2.80,
 // + op_sel broadcasts of dt / du in inline asm (this kernel) 2.78; one-channel kernel 3.26.
+// `a`: planned for kPCh channels per workgroup (plan_fwd, scan_fwd.hip)
 int launch_fwd_pair(const FwdArgs& a, int itype, hipStream_t s) {
-  if (itype == MC_DTYPE_BF16) return launch_pair_t<bf16_t>(a, s);
-  return launch_pair_t<f16_t>(a, s);
+  const dim3 grid(a.total_blocks), block(64);
+  const bool fine = a.chunk_states && a.state_interval == kFineS;   // training forward saving fine states
+  MC_DISPATCH_T16(itype, MC_DISPATCH_BOOL(a.softplus != 0, kSP, MC_DISPATCH_BOOL(fine, kFine, hipLaunchKernelGGL(
+      (scan_fwd_pair_kernel<T, kSP, kFine>), grid, block, (size_t)PairLayout<T>::kRowBytes + PairLayout<T>::kBCBytes,
+      s, a))));
+  return check_launch("mc_scan_fwd");
 }
 
 }  // namespace scan

@@ -106,6 +106,33 @@ def states_interval(L, dim, states):
     raise RuntimeError(f"scan states of shape {tuple(states.shape)} match neither interval (L {L}, dim {dim})")
 
 
+def _fill_common(p, u, delta, A, B, C, D, z, delta_bias, delta_softplus, dirs):
+    """The fields ScanFwdParams and ScanBwdParams share: shape, dtypes, softplus, the input strides and
+    pointers, the grouped directions."""
+    batch, dim, L = delta.shape
+    p.batch, p.dim, p.seqlen, p.dstate, p.n_groups = batch, dim, L, A.shape[1], B.shape[1]
+    p.itype, p.wtype = _lib.dtype_code(u.dtype), _lib.dtype_code(B.dtype)
+    p.delta_softplus = int(bool(delta_softplus))
+    p.u_batch_stride, p.u_dim_stride = u.stride(0), u.stride(1)
+    p.delta_batch_stride, p.delta_dim_stride = delta.stride(0), delta.stride(1)
+    if z is not None:
+        p.z_batch_stride, p.z_dim_stride = z.stride(0), z.stride(1)
+    p.B_batch_stride, p.B_group_stride, p.B_dstate_stride = B.stride(0), B.stride(1), B.stride(2)
+    p.C_batch_stride, p.C_group_stride, p.C_dstate_stride = C.stride(0), C.stride(1), C.stride(2)
+    p.u, p.delta, p.A, p.B, p.C = u.data_ptr(), delta.data_ptr(), A.data_ptr(), B.data_ptr(), C.data_ptr()
+    p.D, p.z, p.delta_bias = _lib.ptr(D), _lib.ptr(z), _lib.ptr(delta_bias)
+    if dirs is not None:
+        p.reverse_groups, p.u_groups = int(dirs[0]), int(dirs[1])
+
+
+def _prep_inputs(rows, A, B, C, D, delta_bias):
+    """What the two autograd forwards do to their inputs: unit stride along L for the rows and B / C
+    (B / C as (B, G, N, L)), contiguous fp32 A / D / delta_bias."""
+    return ([_last_dim_contig(r) for r in rows], _prep_bc(B, "B"), _prep_bc(C, "C"), A.float().contiguous(),
+            D.float().contiguous() if D is not None else None,
+            delta_bias.float().contiguous() if delta_bias is not None else None)
+
+
 def scan_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, want_states, want_last, want_y=False,
              dirs=None):
     """Run mc_scan_fwd.  Returns (out, chunk_states or None, last_state or None[, out_y]).
@@ -127,24 +154,12 @@ def scan_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, want_states, w
     last = (torch.empty(batch, dim, dstate, device=u.device, dtype=torch.float32)
             if want_last and not want_states else None)
     p = _lib.ScanFwdParams()
-    p.batch, p.dim, p.seqlen, p.dstate, p.n_groups = batch, dim, L, dstate, G
-    p.itype, p.wtype = _lib.dtype_code(u.dtype), _lib.dtype_code(B.dtype)
-    p.delta_softplus = int(bool(delta_softplus))
-    p.u_batch_stride, p.u_dim_stride = u.stride(0), u.stride(1)
-    p.delta_batch_stride, p.delta_dim_stride = delta.stride(0), delta.stride(1)
-    if z is not None:
-        p.z_batch_stride, p.z_dim_stride = z.stride(0), z.stride(1)
+    _fill_common(p, u, delta, A, B, C, D, z, delta_bias, delta_softplus, dirs)
     p.out_batch_stride, p.out_dim_stride = out.stride(0), out.stride(1)
-    p.B_batch_stride, p.B_group_stride, p.B_dstate_stride = B.stride(0), B.stride(1), B.stride(2)
-    p.C_batch_stride, p.C_group_stride, p.C_dstate_stride = C.stride(0), C.stride(1), C.stride(2)
-    p.u, p.delta, p.A, p.B, p.C = u.data_ptr(), delta.data_ptr(), A.data_ptr(), B.data_ptr(), C.data_ptr()
-    p.D, p.z, p.delta_bias = _lib.ptr(D), _lib.ptr(z), _lib.ptr(delta_bias)
     p.out, p.last_state = out.data_ptr(), _lib.ptr(last)
     ws_bytes = lib.mc_scan_fwd_workspace_bytes(batch, L, dstate, G)
     ws = torch.empty(max(ws_bytes, 1), device=u.device, dtype=torch.uint8)
     p.workspace, p.workspace_bytes = ws.data_ptr(), ws_bytes
-    if dirs is not None:
-        p.reverse_groups, p.u_groups = int(dirs[0]), int(dirs[1])
     out_y = torch.empty_like(u) if (want_y and z is not None) else None
     if out_y is not None:
         p.out_y, p.out_y_batch_stride, p.out_y_dim_stride = out_y.data_ptr(), out_y.stride(0), out_y.stride(1)
@@ -207,22 +222,12 @@ def scan_bwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, dout, states, 
     ws_bytes = lib.mc_scan_bwd_workspace_bytes(batch, dim, L, dstate, G)
     ws = torch.empty(max(ws_bytes, 1), device=u.device, dtype=torch.uint8)
     p = _lib.ScanBwdParams()
-    p.batch, p.dim, p.seqlen, p.dstate, p.n_groups = batch, dim, L, dstate, G
-    p.itype, p.wtype = _lib.dtype_code(u.dtype), _lib.dtype_code(B.dtype)
-    p.delta_softplus = int(bool(delta_softplus))
-    p.u_batch_stride, p.u_dim_stride = u.stride(0), u.stride(1)
-    p.delta_batch_stride, p.delta_dim_stride = delta.stride(0), delta.stride(1)
-    if z is not None:
-        p.z_batch_stride, p.z_dim_stride = z.stride(0), z.stride(1)
+    _fill_common(p, u, delta, A, B, C, D, z, delta_bias, delta_softplus, dirs)
     p.dout_batch_stride, p.dout_dim_stride = dout.stride(0), dout.stride(1)
     p.du_batch_stride, p.du_dim_stride = du.stride(0), du.stride(1)
     p.ddelta_batch_stride, p.ddelta_dim_stride = ddelta.stride(0), ddelta.stride(1)
     if dz is not None:
         p.dz_batch_stride, p.dz_dim_stride = dz.stride(0), dz.stride(1)
-    p.B_batch_stride, p.B_group_stride, p.B_dstate_stride = B.stride(0), B.stride(1), B.stride(2)
-    p.C_batch_stride, p.C_group_stride, p.C_dstate_stride = C.stride(0), C.stride(1), C.stride(2)
-    p.u, p.delta, p.A, p.B, p.C = u.data_ptr(), delta.data_ptr(), A.data_ptr(), B.data_ptr(), C.data_ptr()
-    p.D, p.z, p.delta_bias = _lib.ptr(D), _lib.ptr(z), _lib.ptr(delta_bias)
     p.dout, p.chunk_states = dout.data_ptr(), states.data_ptr()
     p.state_interval = states_interval(L, dim, states)
     p.du, p.ddelta, p.dz, p.dB, p.dC = du.data_ptr(), ddelta.data_ptr(), _lib.ptr(dz), dB.data_ptr(), dC.data_ptr()
@@ -231,8 +236,6 @@ def scan_bwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, dout, states, 
         p.dC_batch_stride, p.dC_group_stride, p.dC_dstate_stride = dC.stride(0), dC.stride(1), dC.stride(2)
     p.dA, p.dD, p.ddelta_bias = dA.data_ptr(), _lib.ptr(dD), _lib.ptr(dbias)
     p.workspace, p.workspace_bytes = ws.data_ptr(), ws_bytes
-    if dirs is not None:
-        p.reverse_groups, p.u_groups = int(dirs[0]), int(dirs[1])
     if RECORD_DISPATCH:
         DISPATCH.append(("bwd", int(lib.mc_scan_bwd_kernel(p))))
     _lib.check(lib.mc_scan_bwd(p, _lib.stream_handle(u.device)), "mc_scan_bwd")
@@ -245,12 +248,8 @@ class SelectiveScanFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False,
                 return_last_state=False, dz_slab=None, du_handoff=None, dbc_slab=None):
-        u, delta, z = _last_dim_contig(u), _last_dim_contig(delta), _last_dim_contig(z)
         squeeze_B, squeeze_C = B.dim() == 3, C.dim() == 3
-        B, C = _prep_bc(B, "B"), _prep_bc(C, "C")
-        A32 = A.float().contiguous()
-        D32 = D.float().contiguous() if D is not None else None
-        bias32 = delta_bias.float().contiguous() if delta_bias is not None else None
+        (u, delta, z), B, C, A32, D32, bias32 = _prep_inputs((u, delta, z), A, B, C, D, delta_bias)
         _check_inputs(u, delta, A32, B, C, D32, z, bias32)
         need_grad = any(ctx.needs_input_grad[:8])
         out, states, last = scan_fwd(u, delta, A32, B, C, D32, z, bias32, delta_softplus,
@@ -316,11 +315,7 @@ class GroupedScanFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, u, delta, A, B, C, D, delta_bias, delta_softplus, reverse_groups, u_groups):
-        u, delta = _last_dim_contig(u), _last_dim_contig(delta)
-        B, C = _prep_bc(B, "B"), _prep_bc(C, "C")
-        A32 = A.float().contiguous()
-        D32 = D.float().contiguous() if D is not None else None
-        bias32 = delta_bias.float().contiguous() if delta_bias is not None else None
+        (u, delta), B, C, A32, D32, bias32 = _prep_inputs((u, delta), A, B, C, D, delta_bias)
         batch, dim, L = delta.shape
         G = B.shape[1]
         if not (1 <= u_groups <= G and G % u_groups == 0):
